@@ -2,6 +2,7 @@
 """bench.py -- character IK solves/sec on MI355X (BASELINE.json metric) + J-assembly HBM roofline.
 
     python bench.py --gpus N --steps K --warmup W [--batch B] [--config cfg2|cfg2_all|cfg3|cfg5|cfg2_tracker|...]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: a full batched solve (10 Gauss-Newton
 iterations: FK -> Jacobian/residual -> JtJ/Jtr -> Cholesky (+1 refinement) -> theta update) of
@@ -9,7 +10,12 @@ B independent 72-joint humanoid instances per GPU, inputs resident in HBM.  For 
 launches one rank per GPU (torch.distributed.run); instances are sharded (weak scaling: B per GPU
 fixed) and the only collective is one all-reduce of the per-batch residual norms per solve.
 
-Prints ONE JSON line on rank 0 (see the task contract): metric/value/unit/... plus
+A plain run sets up the seeded batch, runs W untimed and K timed steps and prints ONE JSON line on rank 0:
+metric/value/unit/higher_is_better/dtype/ms_per_step/... and "check" with the reduced residual norms of the last
+step.  --dump-outputs DIR writes what the last timed step returned (rank 0's shard) as DIR/<name>.npy: theta, error,
+iterations, status (float32 / float64; a fixed, seeded sample of instances when they would exceed 64 MB, its indices
+in DIR/instances.npy) and the reduced norms; the inputs are the same from run to run.
+--full adds everything else, each part outside the timed region:
   "check":          parity of THIS batch: the first --check-instances (default 1024) DISTINCT instances of
                     the timed batch re-solved by the CPU oracle in double precision; max / median
                     relative pose-parameter difference (north_star bound: 1e-5)
@@ -23,6 +29,7 @@ Prints ONE JSON line on rank 0 (see the task contract): metric/value/unit/... pl
                     target 65536 x 72 (cfg3, LM schedule), the weak-scaling shard 32768 x 72, the wide-J
                     300-joint rig (cfg5), the batched driver's default line search, a tracker-shaped problem (cfg2 +
                     plane block + parameter limits) -- each with its own solves/s, cpu_baseline and parity check
+  and the details file (--details)
 """
 from __future__ import annotations
 
@@ -430,9 +437,36 @@ def solve_loop(db: DeviceBatch, opt, steps, warmup, dist=None, comm=None, dtype=
     elapsed_rank = elapsed
     elapsed = D.reduce_max(dist, elapsed, dev)
     db.last_status = outputs["status"]
+    db.last_outputs = outputs
     db.pb_last_iterations = outputs["iterations"]
     db.last_elapsed_rank = elapsed_rank
     return elapsed, theta, [float(x) for x in norms.tolist()]
+
+
+DUMP_BYTES = 63 * 10**6  # --dump-outputs: the per-instance rows stay below this (64 MB in all with the headers and the norms)
+
+
+def dump_outputs(path, db: DeviceBatch, theta, norms):
+    """What the last timed step returned to its caller, as path/<name>.npy in float32 / float64: theta, error, iterations,
+    status (one row per instance) and the reduced norms.  Above DUMP_BYTES the rows are a fixed, seeded sample of the
+    instances, whose indices go to path/instances.npy."""
+    out = db.last_outputs
+    rows = {
+        "theta": theta.detach().cpu().numpy(),
+        "error": out["error"].cpu().numpy().astype(np.float64),
+        "iterations": out["iterations"].cpu().numpy().astype(np.float64),
+        "status": out["status"].cpu().numpy().astype(np.float64),
+    }
+    per_instance = sum(a[0].nbytes for a in rows.values())
+    if per_instance * db.B > DUMP_BYTES:
+        n = DUMP_BYTES // (per_instance + 8)
+        idx = np.sort(np.random.default_rng(12345).choice(db.B, size=n, replace=False))
+        rows = {k: a[idx] for k, a in rows.items()}
+        rows["instances"] = idx.astype(np.float64)
+    rows["norms"] = np.asarray(norms, np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in rows.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def solved_parameters(pb) -> int:
@@ -648,7 +682,7 @@ def main() -> None:
     ap.add_argument("--check-instances", type=int, default=1024, help="distinct instances of the timed batch re-solved by the oracle (0 = skip)")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the other BASELINE configurations (N = 1 default run reports them)")
     ap.add_argument("--jac-launches", type=int, default=20)
-    ap.add_argument("--measure-traffic", action="store_true", help="measure roofline.traffic in this run (rocprofv3 --pmc over a child process; adds about a minute).  ON by default for the default single-GPU run when rocprofv3 is on the path")
+    ap.add_argument("--measure-traffic", action="store_true", help="measure roofline.traffic in this run (rocprofv3 --pmc over a child process; adds about a minute).  ON by default for the default single-GPU --full run when rocprofv3 is on the path")
     ap.add_argument("--no-measure-traffic", action="store_true", help="never run the rocprofv3 passes: roofline.traffic then comes from the committed pass (profiles/pmc_jacobian.json) and the line says so")
     ap.add_argument("--line-search", type=int, default=0, choices=[0, 1, 2], help="MMX_LINE_SEARCH_*: 0 none (the BASELINE metric), 1 GaussNewtonSolverT's rule, 2 the rule of the batched driver's solvers (SubsetGN / GN-QR)")
     ap.add_argument("--lambda", dest="regularization", type=float, default=0.05, help="GaussNewtonSolverOptions::regularization (the BASELINE metric: 0.05)")
@@ -656,6 +690,8 @@ def main() -> None:
     ap.add_argument("--precision", default="f32", choices=PRECISIONS, help="mmx_gn_options::precision of mmx_solve (mixed: double theta / FK / residuals / g around the single-precision factor; auto: the elements the single-precision solve marks are solved again by the mixed instantiation, what that cannot converge by the double one)")
     ap.add_argument("--driver-defaults", action="store_true", help="the batched driver's real defaults instead of ten fixed iterations (lambda 0.01, 4..50 iterations, threshold 10, line search 2)")
     ap.add_argument("--details", default="", help="where the details of the run go (default gpurun_out/bench_details.json)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step returned (theta, error, iterations, status, the reduced norms) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: the J-assembly roofline, the parity check against the CPU oracle, the CPU baseline, the other BASELINE configurations and the details file")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend (nccl = RCCL; gloo only for the plumbing test)")
     args = ap.parse_args()
 
@@ -703,108 +739,111 @@ def main() -> None:
     elapsed, theta_final, (total_err, total_it, failed) = solve_loop(db, opt, args.steps, args.warmup, dist, comm, args.dtype)
     # per-rank rates (each rank's own clock around the same K steps) next to the aggregate, which uses the slowest rank's time
     rank_rate_min, rank_rate_max = D.reduce_min_max(dist, float(B) * args.steps / db.last_elapsed_rank, pb.device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, db, theta_final, (total_err, total_it, failed))
 
-    # ---- roofline of the J-assembly kernel (mmx_eval_jacobian): HIP events on the launch stream
     M, P = pb.M, pb.P
-    Kp_, Ko_ = len(parents[0]), len(parents[1])
-    jac = torch.empty((B, P, M), dtype=torch.float32, device=dev)
-    res = torch.empty((B, M), dtype=torch.float32, device=dev)
-    err = torch.empty((B,), dtype=torch.float64, device=dev)
-    for _ in range(3):
-        pb.eval_jacobian(theta_star, jac, res, err)
-    torch.cuda.synchronize()
-    # HIP events attached to the kernel's own dispatch packet on the launch stream
-    # (mmx_eval_jacobian_timed -> hipExtLaunchKernelGGL): the kernel's duration as a rocprofv3 kernel
-    # trace reports it, without launch latency or the gap between back-to-back dispatches
-    jac_ms = float(np.mean([pb.eval_jacobian_kernel_ms(theta_star, jac, res, err) for _ in range(args.jac_launches)]))
-    # the same launches bracketed by ordinary recorded events (includes the dispatch latency): reported as context
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.jac_launches)]
-    for a, b in evs:
-        a.record()
-        pb.eval_jacobian(theta_star, jac, res, err)
-        b.record()
-    torch.cuda.synchronize()
-    jac_ms_recorded = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-    bytes_per_launch = B * algorithmic_bytes_per_instance(M, P, Kp_, Ko_)
-    achieved = bytes_per_launch / (jac_ms * 1e-3) / 1e9
-    # HBM traffic of the kernel: measured in THIS run when --measure-traffic is given (two rocprofv3 --pmc passes over a child
-    # process that launches the same kernel on the same shape, scripts/pmc_traffic.py); otherwise the committed pass of the
-    # same shape (profiles/pmc_jacobian.json), and the line says which
-    traffic, traffic_source = None, None
-    default_shape = world == 1 and args.config == "cfg2" and args.batch == 0
-    want_traffic = (args.measure_traffic or default_shape) and not args.no_measure_traffic
-    if want_traffic and rank == 0 and world == 1:
-        traffic = measure_traffic(args.config, B)
-        traffic_source = "rocprofv3 --pmc in this run" if traffic is not None else None
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_jacobian.json")
-    if traffic is None and os.path.exists(pmc_path):
-        try:
-            pm = json.load(open(pmc_path))
-            if pm.get("batch") == B and pm.get("config") == args.config:
-                traffic = pm.get("hbm_bytes_per_launch")
-                traffic_source = "profiles/pmc_jacobian.json (committed rocprofv3 --pmc pass of this shape)"
-        except Exception:
-            traffic = None
-    del jac
-    # context for the roofline: (i) the same kernel at the weak-scaling shard size of BASELINE
-    # configs[3] (32768 instances per GPU), where launch ramp-up and the FK prologue are amortised,
-    # (ii) what a plain write-only fill of the same byte count reaches on this box
-    extra = {}
-    if rank == 0 and world == 1:
-        def timed(fn, n):
-            for _ in range(2):
-                fn()
-            pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
-            for a, b in pairs:
-                a.record()
-                fn()
-                b.record()
-            torch.cuda.synchronize()
-            return float(np.mean([a.elapsed_time(b) for a, b in pairs]))
-
-        fill = torch.empty(bytes_per_launch // 4, dtype=torch.float32, device=dev)
-        fill_ms = timed(lambda: fill.zero_(), 5)
-        extra["fill_same_bytes_gbs"] = bytes_per_launch / (fill_ms * 1e-3) / 1e9
-        # the same stores (layout, workgroup shape, width) without any kinematics: what the write
-        # pattern of a column-major J per instance allows on this box
-        if M == 3 * (Kp_ + 3 * Ko_):  # (the probe replays the stores of position / orientation rows only)
-            for _ in range(2):
-                pb.store_pattern_kernel_ms(fill)
-            sp_ms = float(np.mean([pb.store_pattern_kernel_ms(fill) for _ in range(5)]))
-            extra["store_pattern_gbs"] = B * 4 * M * P / (sp_ms * 1e-3) / 1e9
-        del fill
-        if args.config == "cfg2":
-            for BL in (32768, 65536):  # the weak-scaling shard of BASELINE configs[3] and north_star's target size
-                if B >= BL:
-                    continue
-                dbL = DeviceBatch(rig, parents, BL, local_rank, seed + 1)
-                jacL = torch.empty((BL, P, M), dtype=torch.float32, device=dev)
-                resL = torch.empty((BL, M), dtype=torch.float32, device=dev)
-                errL = torch.empty((BL,), dtype=torch.float64, device=dev)
+    if args.full:
+        # ---- roofline of the J-assembly kernel (mmx_eval_jacobian): HIP events on the launch stream
+        Kp_, Ko_ = len(parents[0]), len(parents[1])
+        jac = torch.empty((B, P, M), dtype=torch.float32, device=dev)
+        res = torch.empty((B, M), dtype=torch.float32, device=dev)
+        err = torch.empty((B,), dtype=torch.float64, device=dev)
+        for _ in range(3):
+            pb.eval_jacobian(theta_star, jac, res, err)
+        torch.cuda.synchronize()
+        # HIP events attached to the kernel's own dispatch packet on the launch stream
+        # (mmx_eval_jacobian_timed -> hipExtLaunchKernelGGL): the kernel's duration as a rocprofv3 kernel
+        # trace reports it, without launch latency or the gap between back-to-back dispatches
+        jac_ms = float(np.mean([pb.eval_jacobian_kernel_ms(theta_star, jac, res, err) for _ in range(args.jac_launches)]))
+        # the same launches bracketed by ordinary recorded events (includes the dispatch latency): reported as context
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.jac_launches)]
+        for a, b in evs:
+            a.record()
+            pb.eval_jacobian(theta_star, jac, res, err)
+            b.record()
+        torch.cuda.synchronize()
+        jac_ms_recorded = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+        bytes_per_launch = B * algorithmic_bytes_per_instance(M, P, Kp_, Ko_)
+        achieved = bytes_per_launch / (jac_ms * 1e-3) / 1e9
+        # HBM traffic of the kernel: measured in THIS run when --measure-traffic is given (two rocprofv3 --pmc passes over a child
+        # process that launches the same kernel on the same shape, scripts/pmc_traffic.py); otherwise the committed pass of the
+        # same shape (profiles/pmc_jacobian.json), and the line says which
+        traffic, traffic_source = None, None
+        default_shape = world == 1 and args.config == "cfg2" and args.batch == 0
+        want_traffic = (args.measure_traffic or default_shape) and not args.no_measure_traffic
+        if want_traffic and rank == 0 and world == 1:
+            traffic = measure_traffic(args.config, B)
+            traffic_source = "rocprofv3 --pmc in this run" if traffic is not None else None
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_jacobian.json")
+        if traffic is None and os.path.exists(pmc_path):
+            try:
+                pm = json.load(open(pmc_path))
+                if pm.get("batch") == B and pm.get("config") == args.config:
+                    traffic = pm.get("hbm_bytes_per_launch")
+                    traffic_source = "profiles/pmc_jacobian.json (committed rocprofv3 --pmc pass of this shape)"
+            except Exception:
+                traffic = None
+        del jac
+        # context for the roofline: (i) the same kernel at the weak-scaling shard size of BASELINE
+        # configs[3] (32768 instances per GPU), where launch ramp-up and the FK prologue are amortised,
+        # (ii) what a plain write-only fill of the same byte count reaches on this box
+        extra = {}
+        if rank == 0 and world == 1:
+            def timed(fn, n):
                 for _ in range(2):
-                    dbL.pb.eval_jacobian(dbL.theta_star, jacL, resL, errL)
-                msL = float(np.mean([dbL.pb.eval_jacobian_kernel_ms(dbL.theta_star, jacL, resL, errL) for _ in range(5)]))
-                gbsL = BL * algorithmic_bytes_per_instance(M, P, Kp_, Ko_) / (msL * 1e-3) / 1e9
-                extra[f"at_batch_{BL}"] = {"achieved": gbsL, "frac": gbsL / HBM_PEAK_GBS, "ms_per_launch": msL}
-                del jacL, resL, errL, dbL
+                    fn()
+                pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+                for a, b in pairs:
+                    a.record()
+                    fn()
+                    b.record()
+                torch.cuda.synchronize()
+                return float(np.mean([a.elapsed_time(b) for a, b in pairs]))
+
+            fill = torch.empty(bytes_per_launch // 4, dtype=torch.float32, device=dev)
+            fill_ms = timed(lambda: fill.zero_(), 5)
+            extra["fill_same_bytes_gbs"] = bytes_per_launch / (fill_ms * 1e-3) / 1e9
+            # the same stores (layout, workgroup shape, width) without any kinematics: what the write
+            # pattern of a column-major J per instance allows on this box
+            if M == 3 * (Kp_ + 3 * Ko_):  # (the probe replays the stores of position / orientation rows only)
+                for _ in range(2):
+                    pb.store_pattern_kernel_ms(fill)
+                sp_ms = float(np.mean([pb.store_pattern_kernel_ms(fill) for _ in range(5)]))
+                extra["store_pattern_gbs"] = B * 4 * M * P / (sp_ms * 1e-3) / 1e9
+            del fill
+            if args.config == "cfg2":
+                for BL in (32768, 65536):  # the weak-scaling shard of BASELINE configs[3] and north_star's target size
+                    if B >= BL:
+                        continue
+                    dbL = DeviceBatch(rig, parents, BL, local_rank, seed + 1)
+                    jacL = torch.empty((BL, P, M), dtype=torch.float32, device=dev)
+                    resL = torch.empty((BL, M), dtype=torch.float32, device=dev)
+                    errL = torch.empty((BL,), dtype=torch.float64, device=dev)
+                    for _ in range(2):
+                        dbL.pb.eval_jacobian(dbL.theta_star, jacL, resL, errL)
+                    msL = float(np.mean([dbL.pb.eval_jacobian_kernel_ms(dbL.theta_star, jacL, resL, errL) for _ in range(5)]))
+                    gbsL = BL * algorithmic_bytes_per_instance(M, P, Kp_, Ko_) / (msL * 1e-3) / 1e9
+                    extra[f"at_batch_{BL}"] = {"achieved": gbsL, "frac": gbsL / HBM_PEAK_GBS, "ms_per_launch": msL}
+                    del jacL, resL, errL, dbL
+                    torch.cuda.empty_cache()
+            if args.config == "cfg2" and not args.no_extra_configs:
+                # ... and on SURVEY 8(d)'s stress variant (P = 219, both constraints on all 72 joints: M = 864, 766 380 B per instance);
+                # (not in the profiling passes, --no-extra-configs: the same kernel name at the same grid size would blur their averages)
+                rigA, parA, _, _, _ = build_rig("cfg2_all")
+                dbA = DeviceBatch(rigA, parA, 4096, local_rank, seed + 2)
+                MA, PA = dbA.pb.M, dbA.pb.P
+                jacA = torch.empty((4096, PA, MA), dtype=torch.float32, device=dev)
+                resA = torch.empty((4096, MA), dtype=torch.float32, device=dev)
+                errA = torch.empty((4096,), dtype=torch.float64, device=dev)
+                for _ in range(2):
+                    dbA.pb.eval_jacobian(dbA.theta_star, jacA, resA, errA)
+                msA = float(np.mean([dbA.pb.eval_jacobian_kernel_ms(dbA.theta_star, jacA, resA, errA) for _ in range(5)]))
+                bpiA = algorithmic_bytes_per_instance(MA, PA, len(parA[0]), len(parA[1]))
+                gbsA = 4096 * bpiA / (msA * 1e-3) / 1e9
+                extra["cfg2_all_at_batch_4096"] = {"achieved": gbsA, "frac": gbsA / HBM_PEAK_GBS, "ms_per_launch": msA, "bytes_per_instance": bpiA}
+                del jacA, resA, errA, dbA
                 torch.cuda.empty_cache()
-        if args.config == "cfg2" and not args.no_extra_configs:
-            # ... and on SURVEY 8(d)'s stress variant (P = 219, both constraints on all 72 joints: M = 864, 766 380 B per instance);
-            # (not in the profiling passes, --no-extra-configs: the same kernel name at the same grid size would blur their averages)
-            rigA, parA, _, _, _ = build_rig("cfg2_all")
-            dbA = DeviceBatch(rigA, parA, 4096, local_rank, seed + 2)
-            MA, PA = dbA.pb.M, dbA.pb.P
-            jacA = torch.empty((4096, PA, MA), dtype=torch.float32, device=dev)
-            resA = torch.empty((4096, MA), dtype=torch.float32, device=dev)
-            errA = torch.empty((4096,), dtype=torch.float64, device=dev)
-            for _ in range(2):
-                dbA.pb.eval_jacobian(dbA.theta_star, jacA, resA, errA)
-            msA = float(np.mean([dbA.pb.eval_jacobian_kernel_ms(dbA.theta_star, jacA, resA, errA) for _ in range(5)]))
-            bpiA = algorithmic_bytes_per_instance(MA, PA, len(parA[0]), len(parA[1]))
-            gbsA = 4096 * bpiA / (msA * 1e-3) / 1e9
-            extra["cfg2_all_at_batch_4096"] = {"achieved": gbsA, "frac": gbsA / HBM_PEAK_GBS, "ms_per_launch": msA, "bytes_per_instance": bpiA}
-            del jacA, resA, errA, dbA
-            torch.cuda.empty_cache()
 
     if rank == 0:
         solves = float(B) * world * args.steps
@@ -853,20 +892,6 @@ def main() -> None:
                       "damping_floored": int((status & 4 != 0).sum()), "precision_suspect": int((status & 8 != 0).sum()),
                       "escalated_f64": int((status & 16 != 0).sum()), "mixed": int((status & 32 != 0).sum())},
             "build": build_stamp(),
-            "roofline": {
-                "kernel": "fkJacobianKernel<true> (mmx_eval_jacobian)",
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_source": traffic_source,
-                "bytes_per_launch": bytes_per_launch,
-                "ms_per_launch": jac_ms,
-                "batch": B,
-                **extra,
-            },
             "roofline_fused": {
                 "kernel": "fusedSolveKernel (mmx_solve; latency-bound, no J formed)",
                 "dense_equivalent_flops_per_solve": dense_flops,
@@ -875,6 +900,23 @@ def main() -> None:
                 "unit": "TFLOP/s (dense-equivalent)",
                 "frac": per_gpu_solves_per_s * dense_flops / 1e12 / FP32_PEAK_TFLOPS,
             },
+        }
+    if rank == 0 and not args.full:
+        print(json.dumps(round_floats(line), separators=(",", ":")), flush=True)
+    if rank == 0 and args.full:
+        line["roofline"] = {
+            "kernel": "fkJacobianKernel<true> (mmx_eval_jacobian)",
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "traffic_source": traffic_source,
+            "bytes_per_launch": bytes_per_launch,
+            "ms_per_launch": jac_ms,
+            "batch": B,
+            **extra,
         }
         details["roofline_fused_pmc"] = fused_pmc()
         details["roofline_timing"] = {"ms_per_launch_recorded_events": jac_ms_recorded, "how": "HIP events attached to the kernel's dispatch packet on the launch stream (hipExtLaunchKernelGGL)"}

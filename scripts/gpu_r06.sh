@@ -27,7 +27,7 @@ case "$step" in
       for lib in default $v; do
         if [ $lib = default ]; then unset MMX_LIB; else export MMX_LIB=$PWD/momentum_amd/libmmx_hip_$v.so; fi
         for cfg in "--config cfg2" "--config cfg3 --steps 4" "--config cfg2 --line-search 2" "--config cfg2 --batch 32768 --steps 8"; do
-          timeout 300 $B $cfg "$@" 2>/dev/null | python -c "
+          timeout 300 $B --full $cfg "$@" 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); print('$lib', '$cfg', 'value %.4g' % l['value'], 'max_rel', l['check'].get('max_rel'), 'median', l['check'].get('median_rel'), l['check'].get('within_bound'))"
         done

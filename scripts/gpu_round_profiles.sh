@@ -9,9 +9,10 @@ export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -q < /dev/null 2>&1 | grep -E "passed|failed|FAILED|rror" | tail -6 > $out/pytest_gpu.txt
 # the DRIVER's command (no arguments): its line and ITS side file are the ones profiles/ keeps (round 5's committed side file was
 # a later profiling pass's: every other bench.py call below writes its details elsewhere)
-timeout 1200 python bench.py --details $out/${r}_bench_details.json < /dev/null > $out/${r}_bench_default.json 2> $out/bench_default.err
+timeout 1200 python bench.py --full --details $out/${r}_bench_details.json < /dev/null > $out/${r}_bench_default.json 2> $out/bench_default.err
 cd /tmp
 B="python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 --no-extra-configs --no-cpu-baseline --check-instances 0 --no-measure-traffic --details $out/profiling_pass_details.json"
+B="$B --full"  # (the J-assembly launches that the traces and counter passes below report run under --full)
 timeout 300 rocprofv3 --kernel-trace --stats -d $out/trace2 -o t -- $B < /dev/null > /dev/null 2> $out/trace2.err
 db=$(find $out/trace2 -name "*.db" | head -1)
 [ -n "$db" ] && timeout 120 python $GRAFT_REPO_ROOT/scripts/rocpd_stats.py "$db" < /dev/null > $out/${r}_bench_kernel_stats.txt
@@ -91,7 +92,7 @@ MMX_PHASE_CLOCKS=1 timeout 300 python scripts/diag_mixed_rate.py < /dev/null 2>&
 MMX_PHASE_CLOCKS=1 timeout 300 python bench.py --no-extra-configs --no-cpu-baseline --no-measure-traffic --check-instances 0 --steps 1 --warmup 0 --line-search 2 --details $out/profiling_pass_details.json < /dev/null 2>&1 | grep -v "amdgpu.ids\|^{" > $out/${r}_phase_clocks.txt
 timeout 300 python scripts/diag_precision.py lm 65536 16384 < /dev/null 2>&1 | grep -v amdgpu.ids | tail -2 > $out/lm_steps.txt
 (timeout 120 python scripts/diag_lm_estimate.py < /dev/null 2>&1 | grep cfg3; timeout 900 python scripts/diag_precision.py estimate < /dev/null 2>&1 | grep -E "^cfg|^p128") > $out/${r}_precision_estimate.txt
-timeout 300 python bench.py --config cfg4 --steps 6 --warmup 2 --no-extra-configs --no-cpu-baseline --check-instances 256 < /dev/null > $out/${r}_bench_cfg4.json 2> /dev/null
+timeout 300 python bench.py --full --config cfg4 --steps 6 --warmup 2 --no-extra-configs --no-cpu-baseline --check-instances 256 < /dev/null > $out/${r}_bench_cfg4.json 2> /dev/null
 timeout 200 python scripts/diag_determinism.py 6 < /dev/null 2>&1 | grep -v amdgpu.ids > $out/determinism.txt
 bash scripts/resource_usage.sh > $out/${r}_kernel_resource_usage.txt 2>&1
 # LDS bank conflicts by phase (counter passes over launches cut after successive stamps), eager against graph replay, AUTO's trace

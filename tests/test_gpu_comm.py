@@ -60,7 +60,7 @@ def test_bench_two_ranks_over_rccl_when_two_gpus_are_visible(torch_cuda):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "1024", "--no-cpu-baseline", "--check-instances", "64"]  # fmt: skip
+           "--batch", "1024", "--full", "--no-cpu-baseline", "--check-instances", "64"]  # fmt: skip
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
