@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define MMX_ABI_VERSION 11 /* 6: per-instance characters and constraint parents, MMX_STEP_TRUST_REGION (+ mmx_gn_options::
+#define MMX_ABI_VERSION 12 /* 6: per-instance characters and constraint parents, MMX_STEP_TRUST_REGION (+ mmx_gn_options::
                              trust_region_radius), mmx_comm_* (RCCL), MMX_LIMIT_MINMAX_JOINT_PASSIVE, row-major J
                              7: mmx_tuning / mmx_problem_set_tuning / mmx_problem_last_route (replace the MMX_* environment
                              switches of earlier builds: the library reads no environment variable on the solve path)
@@ -63,6 +63,8 @@ extern "C" {
                                 the single-precision rate), which is also what MMX_PRECISION_AUTO now escalates to where it
                                 applies; status bit MMX_SOLVE_MIXED; mmx_tuning grows mixed_tolerance / mixed_max_cg out of
                                 its reserved words (same size).
+                             12: joint-block types MMX_JC_PROJECTION (two rows) / MMX_JC_DISTANCE; mmx_joint_constraint_block
+                                grows by `projection` / `near_clip` (the array stride of joint_blocks changes).
                              A caller MUST compare mmx_abi_version() with the MMX_ABI_VERSION it was compiled against
                              before any other call: the structs below grow at their end from version to version. */
 #define MMX_PARAMS_PER_JOINT 7 /* momentum/character/types.h:21 */
@@ -287,9 +289,24 @@ typedef struct mmx_ellipsoid_limit {
  *   MMX_JC_FIXED_AXIS_COS     FixedAxisCosErrorFunctionT   :28-39                               1  as above
  *   MMX_JC_FIXED_AXIS_ANGLE   FixedAxisAngleErrorFunctionT :41-66                               1  as above
  *   MMX_JC_NORMAL             NormalErrorFunctionT normal_error_function.cpp:14-31              1  local_point, local_dir=localNormal (normalised), global=globalPoint
+ *   MMX_JC_PROJECTION         ProjectionErrorFunctionT (see the note below)                     2  local_point=offset, projection=P, global=(u, v, ignored), near_clip
+ *   MMX_JC_DISTANCE           DistanceErrorFunctionT   (see the note below)                     1  local_point=offset, global=origin, plane_d=target distance
  * Vectors are normalised on ingest exactly where the reference's data constructors do
  * (plane_error_function.h:30, aim_error_function.h:34, fixed_axis_error_function.h:29-30,
  * normal_error_function.h:34).
+ *
+ * The two point functions of ABI 12, with x = T_parent * offset (the point of a position constraint, t + s R o):
+ *   MMX_JC_PROJECTION  p = A x + a with P = [A | a] (3 x 4 row-major, [B][count][12]).  p.z < near_clip: the constraint is
+ *                      skipped (no error, rows zero).  Otherwise f = (p.x / p.z - u, p.y / p.z - v),
+ *                      df/dx = (1 / p.z) [A_0 - (p.x / p.z) A_2 ; A_1 - (p.y / p.z) A_2] (A_i: row i of A).
+ *   MMX_JC_DISTANCE    f = |x - origin| - d, df/dx = (x - origin)^T / |x - origin| (zero where the norm is zero).
+ * Both are weighted like every block above (error fw * w * |f|^2, rows sqrt(fw * w) f) and take the L2 loss only: a block of
+ * either type with another loss (loss_c > 0 and (alpha, c) != (2, 1)) is refused with MMX_ERR_UNSUPPORTED.
+ * PROVENANCE: these restate momentum's ProjectionErrorFunctionT (ProjectionConstraintDataT: projection, parent, offset,
+ * weight, target; constructor argument nearClip, default 1) and DistanceErrorFunctionT (DistanceConstraintDataT: origin,
+ * target, parent, offset, weight) from memory of the reference, without a checkout at hand, so they carry no file:line
+ * citations yet.  To confirm against the reference: the near-clip test p.z < nearClip and its default of 1; that neither
+ * function applies a constant weight factor (like kPositionWeight); that neither takes a robust loss.
  */
 #define MMX_JC_PLANE 0
 #define MMX_JC_HALF_PLANE 1
@@ -299,6 +316,8 @@ typedef struct mmx_ellipsoid_limit {
 #define MMX_JC_FIXED_AXIS_COS 5
 #define MMX_JC_FIXED_AXIS_ANGLE 6
 #define MMX_JC_NORMAL 7
+#define MMX_JC_PROJECTION 8 /* ABI 12 */
+#define MMX_JC_DISTANCE 9 /* ABI 12 */
 #define MMX_MAX_JOINT_BLOCKS 8
 
 typedef struct mmx_joint_constraint_block {
@@ -308,10 +327,13 @@ typedef struct mmx_joint_constraint_block {
   const float* local_point; /* [B][count][3] or NULL when the type has no point */
   const float* local_dir; /* [B][count][3] or NULL when the type has no direction */
   const float* global; /* [B][count][3] */
-  const float* plane_d; /* [B][count] (plane types only) */
+  const float* plane_d; /* [B][count] (plane types; MMX_JC_DISTANCE: the target distance) */
   const float* weight; /* [B][count] ConstraintData::weight */
   float function_weight; /* SkeletonErrorFunction::weight_ */
   float loss_alpha, loss_c; /* GeneralizedLossT(alpha, c); c <= 0: default L2, c = 1 */
+  /* ---- ABI 12 */
+  const float* projection; /* [B][count][12] MMX_JC_PROJECTION only: 3 x 4 row-major camera matrix, same memory kind */
+  float near_clip; /* MMX_JC_PROJECTION only: constraints with p.z < near_clip are skipped (must be finite) */
 } mmx_joint_constraint_block;
 
 typedef struct mmx_constraint_data {

@@ -49,7 +49,8 @@ namespace {
 struct Prepared {
   mmx_problem* pb = nullptr;
   mmx_gn_options o{};
-  std::vector<float> fw;
+  std::vector<float> fw, uvw; // per-element function weights; projection targets padded to (u, v, 0)
+  mmx_joint_constraint_block blocks[2];
   ~Prepared() { mmx_problem_destroy(pb); }
 };
 
@@ -73,18 +74,51 @@ void prepare(Prepared& p, mmx_rig* rig, const momentum::ParameterSet& activePara
   cd.ori_offset = t.orientationOffsets, cd.ori_target = t.orientationTargets, cd.ori_weight = t.orientationWeights;
   cd.pos_function_weight = cd.ori_function_weight = 1.f; // the per-element weights below carry setWeight()
   cd.memory = MMX_MEM_HOST;
+  // Projection / Distance error functions: one joint-constraint block each, projection first
+  int nb = 0, slot[2] = {-1, -1}; // slot[k]: block of error function 2 + k
+  if (t.numProjections > 0) {
+    p.uvw.assign(size_t(t.nBatch) * size_t(t.numProjections) * 3, 0.f);
+    for (size_t i = 0; i < size_t(t.nBatch) * size_t(t.numProjections); ++i) {
+      p.uvw[3 * i] = t.projectionTargets[2 * i], p.uvw[3 * i + 1] = t.projectionTargets[2 * i + 1];
+    }
+    mmx_joint_constraint_block& k = p.blocks[nb];
+    k = mmx_joint_constraint_block{};
+    k.type = MMX_JC_PROJECTION, k.count = t.numProjections, k.parent = t.projectionParents;
+    k.local_point = t.projectionOffsets, k.global = p.uvw.data(), k.weight = t.projectionWeights;
+    k.projection = t.projections, k.near_clip = t.projectionNearClip, k.function_weight = 1.f;
+    slot[0] = nb++;
+  }
+  if (t.numDistances > 0) {
+    mmx_joint_constraint_block& k = p.blocks[nb];
+    k = mmx_joint_constraint_block{};
+    k.type = MMX_JC_DISTANCE, k.count = t.numDistances, k.parent = t.distanceParents;
+    k.local_point = t.distanceOffsets, k.global = t.distanceOrigins, k.plane_d = t.distanceTargets, k.weight = t.distanceWeights;
+    k.function_weight = 1.f;
+    slot[1] = nb++;
+  }
+  cd.num_joint_blocks = nb;
+  cd.joint_blocks = nb > 0 ? p.blocks : nullptr;
   // errorFunctionWeights [nBatch][numWeightColumns] + weightsMap (tensor_ik.cpp:100-101): one column per block in the ABI's
-  // order (position, orientation); weightsMap[iErr] < 0 means weight 0 (tensor_ik_utility.cpp:176)
-  p.fw.assign(size_t(t.nBatch) * 2, 1.f);
+  // order (position, orientation, limits, model parameters, joint block i at 4 + i); weightsMap[iErr] < 0 means weight 0
+  // (tensor_ik_utility.cpp:176)
+  const int cols = nb > 0 ? 4 + nb : 2;
+  p.fw.assign(size_t(t.nBatch) * size_t(cols), 1.f);
   if (t.errorFunctionWeights != nullptr) {
+    auto weightOf = [&](int64_t b, int iErr) {
+      const int col = t.weightsMap[iErr];
+      return col < 0 ? 0.f : t.errorFunctionWeights[size_t(b) * size_t(t.numWeightColumns) + size_t(col)];
+    };
     for (int64_t b = 0; b < t.nBatch; ++b) {
-      for (int k = 0; k < 2; ++k) {
-        const int col = t.weightsMap[k];
-        p.fw[size_t(2 * b + k)] = col < 0 ? 0.f : t.errorFunctionWeights[size_t(b) * size_t(t.numWeightColumns) + size_t(col)];
+      float* row = p.fw.data() + size_t(b) * size_t(cols);
+      row[0] = weightOf(b, 0), row[1] = weightOf(b, 1);
+      for (int e = 0; e < 2; ++e) {
+        if (slot[e] >= 0) {
+          row[4 + slot[e]] = weightOf(b, 2 + e);
+        }
       }
     }
     cd.function_weights = p.fw.data();
-    cd.num_function_weights = 2;
+    cd.num_function_weights = cols;
   }
   MT_THROW_IF(mmx_problem_set_constraints_sized(pb, &cd, sizeof(cd), nullptr) != MMX_OK, mmx_last_error());
   mmx_gn_options_default(&p.o);

@@ -31,9 +31,21 @@ struct BatchTensors {
   const int32_t* orientationParents = nullptr; // [numOrientations]
   const float *positionOffsets = nullptr, *positionTargets = nullptr, *positionWeights = nullptr; // [B][K][3], [B][K][3], [B][K]
   const float *orientationOffsets = nullptr, *orientationTargets = nullptr, *orientationWeights = nullptr; // [B][K][4] (x,y,z,w), .., [B][K]
+  // ProjectionErrorFunction: 2D targets through a 3 x 4 row-major camera matrix per constraint (MMX_JC_PROJECTION)
+  int32_t numProjections = 0;
+  const int32_t* projectionParents = nullptr; // [numProjections]
+  const float *projectionOffsets = nullptr, *projections = nullptr; // [B][K][3], [B][K][12]
+  const float *projectionTargets = nullptr, *projectionWeights = nullptr; // [B][K][2] (u, v), [B][K]
+  float projectionNearClip = 1.f;
+  // DistanceErrorFunction: distance of a joint point from an origin (MMX_JC_DISTANCE)
+  int32_t numDistances = 0;
+  const int32_t* distanceParents = nullptr; // [numDistances]
+  const float *distanceOffsets = nullptr, *distanceOrigins = nullptr; // [B][K][3], [B][K][3]
+  const float *distanceTargets = nullptr, *distanceWeights = nullptr; // [B][K], [B][K]
   const float* errorFunctionWeights = nullptr; // [B][numWeightColumns] or null
   int numWeightColumns = 0;
-  int weightsMap[2] = {0, 1}; // column of the position / orientation error function, < 0: switched off
+  // column of the position / orientation / projection / distance error function, < 0: switched off
+  int weightsMap[4] = {0, 1, 2, 3};
   const float* perElementTranslationOffsets = nullptr; // [B][J][3] or null: characters[iBatch] of one topology
   const float* perElementPreRotations = nullptr; // [B][J][4] or null
   const int32_t* perElementPositionParents = nullptr; // [B][numPositions] or null

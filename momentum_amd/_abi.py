@@ -14,7 +14,7 @@ c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
 c_uint8_p = C.POINTER(C.c_uint8)
 
-MMX_ABI_VERSION = 11
+MMX_ABI_VERSION = 12
 MMX_OK = 0
 MMX_SOLVE_OK, MMX_SOLVE_NONFINITE, MMX_SOLVE_NOT_PD = 0, 1, 2
 MMX_SOLVE_DAMPING_FLOORED = 4  # informational bit of status[] (include/mmx.h)
@@ -141,12 +141,15 @@ def ellipsoid_array(items):
 
 MMX_JC_PLANE, MMX_JC_HALF_PLANE, MMX_JC_AIM_DIST, MMX_JC_AIM_DIR = 0, 1, 2, 3
 MMX_JC_FIXED_AXIS_DIFF, MMX_JC_FIXED_AXIS_COS, MMX_JC_FIXED_AXIS_ANGLE, MMX_JC_NORMAL = 4, 5, 6, 7
+MMX_JC_PROJECTION, MMX_JC_DISTANCE = 8, 9  # ABI 12
 MMX_MAX_JOINT_BLOCKS = 8
 
 
 def jc_func_dim(type_: int) -> int:
     """FuncDim of the block's error function (rows per constraint)."""
-    return 3 if type_ in (MMX_JC_AIM_DIST, MMX_JC_AIM_DIR, MMX_JC_FIXED_AXIS_DIFF) else 1
+    if type_ in (MMX_JC_AIM_DIST, MMX_JC_AIM_DIR, MMX_JC_FIXED_AXIS_DIFF):
+        return 3
+    return 2 if type_ == MMX_JC_PROJECTION else 1
 
 
 class JointConstraintBlock(C.Structure):
@@ -164,18 +167,22 @@ class JointConstraintBlock(C.Structure):
         ("function_weight", C.c_float),
         ("loss_alpha", C.c_float),
         ("loss_c", C.c_float),
+        # ABI 12
+        ("projection", C.c_void_p),
+        ("near_clip", C.c_float),
     ]
 
 
 class JointBlock:
     """Python-side description of one further joint-constraint block (Plane / Aim / FixedAxis /
-    Normal error function).  Payload arrays are numpy ([K,..] for one instance or [B,K,..]) or,
-    for the device path, contiguous float32 cuda tensors [B,K,..]."""
+    Normal / Projection / Distance error function).  Payload arrays are numpy ([K,..] for one instance or
+    [B,K,..]) or, for the device path, contiguous float32 cuda tensors [B,K,..].  `projection` holds the
+    projection block's 3 x 4 row-major camera matrices (12 floats per constraint)."""
 
-    FIELDS = (("local_point", 3), ("local_dir", 3), ("global_", 3), ("plane_d", 0), ("weight", 0))
+    FIELDS = (("local_point", 3), ("local_dir", 3), ("global_", 3), ("plane_d", 0), ("weight", 0), ("projection", 12))
 
     def __init__(self, type, parent, weight, global_, local_point=None, local_dir=None, plane_d=None,
-                 function_weight: float = 1.0, loss=(2.0, 1.0)):  # fmt: skip
+                 function_weight: float = 1.0, loss=(2.0, 1.0), projection=None, near_clip: float = 1.0):  # fmt: skip
         self.type = int(type)
         self.parent = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
         self.count = int(self.parent.shape[0])
@@ -183,6 +190,8 @@ class JointBlock:
         self.local_point, self.local_dir, self.plane_d = local_point, local_dir, plane_d
         self.function_weight = float(function_weight)
         self.loss = (float(loss[0]), float(loss[1]))
+        self.projection = projection
+        self.near_clip = float(near_clip)
 
     @property
     def rows(self) -> int:
@@ -197,7 +206,8 @@ class JointBlock:
             return a.reshape(shp)[b]
 
         return JointBlock(self.type, self.parent, cut(self.weight, 0), cut(self.global_, 3), cut(self.local_point, 3),
-                          cut(self.local_dir, 3), cut(self.plane_d, 0), self.function_weight, self.loss)  # fmt: skip
+                          cut(self.local_dir, 3), cut(self.plane_d, 0), self.function_weight, self.loss,
+                          cut(self.projection, 12), self.near_clip)  # fmt: skip
 
     def struct(self, keep: list, batch=None, device: bool = False) -> JointConstraintBlock:
         """ctypes struct; arrays it points to are appended to `keep`.  batch = B checks [B,K,..] shapes."""
@@ -222,6 +232,7 @@ class JointBlock:
         return JointConstraintBlock(
             self.type, self.count, C.c_void_p(self.parent.ctypes.data if self.count else 0), ptrs["local_point"], ptrs["local_dir"],
             ptrs["global_"], ptrs["plane_d"], ptrs["weight"], self.function_weight, self.loss[0], self.loss[1],
+            ptrs["projection"], self.near_clip,
         )  # fmt: skip
 
 

@@ -329,8 +329,10 @@ class Problem:
         constraint arrays.  Adds len(limits) + (P if model_target is given) rows to J / r.
         pos_loss / ori_loss: GeneralizedLoss (alpha, c) of the two joint-constraint blocks
         (alpha 2 = L2, 1 = L1, 0 = Cauchy, _abi.MMX_LOSS_WELSCH = Welsch, else Barron's general form).
-        joint_blocks: list of _abi.JointBlock (Plane / Aim / FixedAxis / Normal error functions), payload
-        of the same memory kind as the constraint arrays; their rows follow the orientation rows.
+        joint_blocks: list of _abi.JointBlock (Plane / Aim / FixedAxis / Normal / Projection / Distance error
+        functions), payload of the same memory kind as the constraint arrays; their rows follow the orientation rows
+        (two per projection constraint: its `projection` holds 12 floats per constraint, `near_clip` the depth below
+        which a constraint is skipped; L2 loss only for projection and distance blocks).
         function_weights: [B, C] per-element error-function weights (errorFunctionWeights of solveTensorIKProblem), columns
         position, orientation, limits, model parameters, joint block 0, ...; same memory kind as the constraint arrays."""
         import torch

@@ -9,6 +9,7 @@
 #include <dlfcn.h>
 
 #include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -194,7 +195,7 @@ struct mmx_problem {
   struct JointBlockHost {
     int32_t type = 0, count = 0;
     std::vector<int32_t> parent;
-    DevBuf oLocalPoint, oLocalDir, oGlobal, oPlaneD, oWeight; // owned copies of a host payload
+    DevBuf oLocalPoint, oLocalDir, oGlobal, oPlaneD, oWeight, oProjection; // owned copies of a host payload
   };
   std::vector<std::unique_ptr<JointBlockHost>> blocks;
   std::vector<mmx::JointBlockDev> blockDev;
@@ -372,7 +373,8 @@ int32_t uploadProblemTables(mmx_problem* pb) {
       }
     }
     // joints that carry a further joint error function or an ellipsoid limit count like constrained joints for the
-    // structure (solve list, source slots): point-like ones see every dof above them, fixed-axis ones rotations only
+    // structure (solve list, source slots): point-like ones (projection and distance among them) see every dof above them,
+    // fixed-axis ones rotations only
     std::vector<int32_t> structPos, structOri;
     if (pb->instPos) {
       structPos = pb->unionPos;
@@ -1668,24 +1670,34 @@ int32_t mmx_problem_set_constraints(mmx_problem* pb, const mmx_constraint_data* 
   for (int32_t i = 0; i < c->num_joint_blocks; ++i) {
     const mmx_joint_constraint_block& jb = c->joint_blocks[i];
     const std::string tag = "joint block " + std::to_string(i);
-    if (jb.type < MMX_JC_PLANE || jb.type > MMX_JC_NORMAL) {
+    if (jb.type < MMX_JC_PLANE || jb.type > MMX_JC_DISTANCE) {
       return fail(MMX_ERR_UNSUPPORTED, tag + ": unknown error-function type");
+    }
+    const bool pointOnly = jb.type == MMX_JC_PROJECTION || jb.type == MMX_JC_DISTANCE; // (ABI 12)
+    if (pointOnly && jb.loss_c > 0.f && !(jb.loss_alpha == 2.f && jb.loss_c == 1.f)) {
+      return fail(MMX_ERR_UNSUPPORTED, tag + ": projection / distance blocks take the L2 loss only (loss_c <= 0 or (alpha, c) = (2, 1))");
+    }
+    if (jb.type == MMX_JC_PROJECTION && !std::isfinite(jb.near_clip)) {
+      return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": near_clip is not finite");
     }
     if (jb.count < 0 || (jb.count > 0 && (jb.parent == nullptr || jb.global == nullptr || jb.weight == nullptr))) {
       return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": negative count or null parent / global / weight array");
     }
     const bool plane = jb.type == MMX_JC_PLANE || jb.type == MMX_JC_HALF_PLANE;
     const bool fixedAxis = jb.type == MMX_JC_FIXED_AXIS_DIFF || jb.type == MMX_JC_FIXED_AXIS_COS || jb.type == MMX_JC_FIXED_AXIS_ANGLE;
-    if (jb.count > 0 && ((!fixedAxis && jb.local_point == nullptr) || (!plane && jb.local_dir == nullptr) || (plane && jb.plane_d == nullptr))) {
+    const bool needD = plane || jb.type == MMX_JC_DISTANCE;
+    if (jb.count > 0 && ((!fixedAxis && jb.local_point == nullptr) || (!plane && !pointOnly && jb.local_dir == nullptr) || (needD && jb.plane_d == nullptr))) {
       return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": a payload array its error function needs is null");
+    }
+    if (jb.count > 0 && jb.type == MMX_JC_PROJECTION && jb.projection == nullptr) {
+      return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": projection block without its projection matrices");
     }
     for (int32_t k = 0; k < jb.count; ++k) {
       if (jb.parent[k] < 0 || jb.parent[k] >= pb->rig->J) {
         return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": parent joint out of range"); // MT_CHECK joint_error_function-inl.h:230
       }
     }
-    const bool three = jb.type == MMX_JC_AIM_DIST || jb.type == MMX_JC_AIM_DIR || jb.type == MMX_JC_FIXED_AXIS_DIFF;
-    genRows += (three ? 3 : 1) * jb.count;
+    genRows += mmx::jointBlockFuncDim(jb.type) * jb.count;
     genCount += jb.count;
     if (!blocksChanged) {
       const mmx_problem::JointBlockHost& h = *pb->blocks[size_t(i)];
@@ -1776,6 +1788,7 @@ int32_t mmx_problem_set_constraints(mmx_problem* pb, const mmx_constraint_data* 
       k.rowStart = row;
       k.fw = jb.function_weight;
       k.loss = makeLoss(jb.loss_alpha, jb.loss_c);
+      k.nearClip = jb.type == MMX_JC_PROJECTION ? jb.near_clip : 0.f;
       const size_t cnt = B * size_t(jb.count);
       auto bring = [&](DevBuf& buf, const float* src, size_t count, const float*& dst) -> hipError_t {
         if (src == nullptr || count == 0) {
@@ -1798,9 +1811,9 @@ int32_t mmx_problem_set_constraints(mmx_problem* pb, const mmx_constraint_data* 
       MMX_HIP(bring(h.oGlobal, jb.global, 3 * cnt, k.global));
       MMX_HIP(bring(h.oPlaneD, jb.plane_d, cnt, k.planeD));
       MMX_HIP(bring(h.oWeight, jb.weight, cnt, k.weight));
-      const bool three = jb.type == MMX_JC_AIM_DIST || jb.type == MMX_JC_AIM_DIR || jb.type == MMX_JC_FIXED_AXIS_DIFF;
+      MMX_HIP(bring(h.oProjection, jb.type == MMX_JC_PROJECTION ? jb.projection : nullptr, 12 * cnt, k.projection));
       first += jb.count;
-      row += (three ? 3 : 1) * jb.count;
+      row += mmx::jointBlockFuncDim(jb.type) * jb.count;
     }
   }
   pb->genRows = genRows;

@@ -241,7 +241,7 @@ struct LimitDev {
 };
 
 // == mmx_joint_constraint_block (include/mmx.h) for the device: one further JointErrorFunctionT
-// specialisation (Plane / Aim / FixedAxis / Normal) with `count` constraints per instance
+// specialisation (Plane / Aim / FixedAxis / Normal / Projection / Distance) with `count` constraints per instance
 struct JointBlockDev {
   int32_t type, count;
   int32_t first; // index of the block's first constraint in the flattened list (genJoint, genTin, genBlock)
@@ -253,6 +253,8 @@ struct JointBlockDev {
   const float* weight; // [B][count]
   float fw; // SkeletonErrorFunction::weight_
   LossDev loss;
+  const float* projection; // [B][count][12] MMX_JC_PROJECTION: 3 x 4 row-major camera matrix, else null
+  float nearClip; // MMX_JC_PROJECTION
 };
 
 // == mmx_ellipsoid_limit (include/mmx.h) + the DFS indices the kernels test ancestry with
@@ -714,7 +716,7 @@ __device__ __forceinline__ F3 sourceDerivative(const ColumnSourceDev& s, const f
 // ---------------------------------------------------------------------------------------------
 // evalFunction of the further JointErrorFunctionT specialisations + the weighting of
 // JointErrorFunctionT::getJacobian (joint_error_function-inl.h:197-226): one constraint with up to
-// one point v_p (NumPos) and one direction v_n, FuncDim = nrows in {1, 3}, df/dv_p = dp, df/dv_n = dn
+// one point v_p (NumPos) and one direction v_n, FuncDim = nrows in {1, 2, 3}, df/dv_p = dp, df/dv_n = dn
 // (row-major, rows >= nrows zero).
 // ---------------------------------------------------------------------------------------------
 struct JointEval {
@@ -732,8 +734,9 @@ __device__ __forceinline__ F3 normalizedOrSame(const F3& a) { // Eigen normalize
   return n2 > 0.f ? (1.f / sqrtf(n2)) * a : a;
 }
 
-__device__ __forceinline__ int jointBlockFuncDim(int type) {
-  return (type == MMX_JC_AIM_DIST || type == MMX_JC_AIM_DIR || type == MMX_JC_FIXED_AXIS_DIFF) ? 3 : 1;
+// (host twin: jointBlockRows in mmx_capi.hip)
+__host__ __device__ __forceinline__ int jointBlockFuncDim(int type) {
+  return (type == MMX_JC_AIM_DIST || type == MMX_JC_AIM_DIR || type == MMX_JC_FIXED_AXIS_DIFF) ? 3 : type == MMX_JC_PROJECTION ? 2 : 1;
 }
 
 __device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k, const float* js, int joint, size_t c) {
@@ -747,7 +750,8 @@ __device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k,
   o.sigma = o.werr = 0.f;
   o.nrows = jointBlockFuncDim(k.type);
   o.hasPoint = k.type != MMX_JC_FIXED_AXIS_DIFF && k.type != MMX_JC_FIXED_AXIS_COS && k.type != MMX_JC_FIXED_AXIS_ANGLE;
-  o.hasDir = k.type != MMX_JC_PLANE && k.type != MMX_JC_HALF_PLANE;
+  o.hasDir = k.type != MMX_JC_PLANE && k.type != MMX_JC_HALF_PLANE && k.type != MMX_JC_PROJECTION && k.type != MMX_JC_DISTANCE;
+  bool skip = false; // a projection behind the near plane: no error, rows zero
   const float* w = js + kJs * joint;
   const F3 t{w[0], w[1], w[2]};
   const Q4 q{w[3], w[4], w[5], w[6]};
@@ -828,6 +832,30 @@ __device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k,
       }
       break;
     }
+    case MMX_JC_PROJECTION: { // p = A x + a ; f = p.xy / p.z - (u, v) ; df/dx = (1 / p.z) [A_0 - f_x A_2 ; A_1 - f_y A_2]
+      const float* m = k.projection + 12 * c;
+      const F3 a0{m[0], m[1], m[2]}, a1{m[4], m[5], m[6]}, a2{m[8], m[9], m[10]};
+      const float pz = dot(a2, o.vp) + m[11];
+      if (pz < k.nearClip) {
+        skip = true;
+        break;
+      }
+      const float iz = 1.f / pz;
+      const float px = (dot(a0, o.vp) + m[3]) * iz, py = (dot(a1, o.vp) + m[7]) * iz;
+      o.f[0] = px - gl.x, o.f[1] = py - gl.y;
+      setRow(o.dp, a0 - px * a2, iz);
+      setRow(o.dp + 3, a1 - py * a2, iz);
+      break;
+    }
+    case MMX_JC_DISTANCE: { // f = |x - origin| - d ; df/dx = (x - origin)^T / |x - origin|
+      const F3 diff = o.vp - gl;
+      const float nrm = sqrtf(dot(diff, diff));
+      o.f[0] = nrm - k.planeD[c];
+      if (nrm > 0.f) {
+        setRow(o.dp, diff, 1.f / nrm);
+      }
+      break;
+    }
     default: { // MMX_JC_NORMAL, normal_error_function.cpp:14-31
       const F3 dist = o.vp - gl;
       o.f[0] = dot(o.vn, dist);
@@ -837,7 +865,7 @@ __device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k,
     }
   }
   const float cw = k.weight[c];
-  if (cw != 0.f && k.fw > 0.f) { // :197-199 ; blocks with weight_ <= 0 are skipped (skeleton_solver_function.cpp:223-231)
+  if (!skip && cw != 0.f && k.fw > 0.f) { // :197-199 ; blocks with weight_ <= 0 are skipped (skeleton_solver_function.cpp:223-231)
     const float sqr = o.f[0] * o.f[0] + o.f[1] * o.f[1] + o.f[2] * o.f[2];
     const float wgt = cw * k.fw;
     o.werr = wgt * lossValue(k.loss, sqr); // :207

@@ -219,7 +219,7 @@ __device__ double paramRowsErrorF64(const RigDev& rig, const ProblemDev& pb, con
 
 // SkeletonSolverFunctionT<double>::getError (skeleton_solver_function.cpp:64-83; rounded through float, :82)
 // The further JointErrorFunctionT<double> specialisations (Plane / HalfPlane, AimDist / AimDir, FixedAxisDiff / Cos /
-// Angle, Normal): evalFunction + the weighting of getJacobian in double -- evalJointConstraint of mmx_device.hpp with T =
+// Angle, Normal, Projection, Distance): evalFunction + the weighting of getJacobian in double -- evalJointConstraint of mmx_device.hpp with T =
 // double (the constraint data stay float like the reference's tensors; joint_error_function-inl.h:197-226).
 struct JointEvalD {
   D3 vp, vn;
@@ -246,7 +246,8 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
   o.sigma = o.werr = 0.0;
   o.nrows = jointBlockFuncDim(k.type);
   o.hasPoint = k.type != MMX_JC_FIXED_AXIS_DIFF && k.type != MMX_JC_FIXED_AXIS_COS && k.type != MMX_JC_FIXED_AXIS_ANGLE;
-  o.hasDir = k.type != MMX_JC_PLANE && k.type != MMX_JC_HALF_PLANE;
+  o.hasDir = k.type != MMX_JC_PLANE && k.type != MMX_JC_HALF_PLANE && k.type != MMX_JC_PROJECTION && k.type != MMX_JC_DISTANCE;
+  bool skip = false; // a projection behind the near plane: no error, rows zero
   const ldsd* w = js + kDs * joint;
   const D3 t{w[0], w[1], w[2]};
   const DQ q{w[3], w[4], w[5], w[6]};
@@ -327,6 +328,30 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
       }
       break;
     }
+    case MMX_JC_PROJECTION: { // p = A x + a ; f = p.xy / p.z - (u, v) ; df/dx = (1 / p.z) [A_0 - f_x A_2 ; A_1 - f_y A_2]
+      const float* m = k.projection + 12 * c;
+      const D3 a0{m[0], m[1], m[2]}, a1{m[4], m[5], m[6]}, a2{m[8], m[9], m[10]};
+      const double pz = ddot(a2, o.vp) + double(m[11]);
+      if (pz < double(k.nearClip)) {
+        skip = true;
+        break;
+      }
+      const double iz = 1.0 / pz;
+      const double px = (ddot(a0, o.vp) + double(m[3])) * iz, py = (ddot(a1, o.vp) + double(m[7])) * iz;
+      o.f[0] = px - gl.x, o.f[1] = py - gl.y;
+      setRow(o.dp, a0 - px * a2, iz);
+      setRow(o.dp + 3, a1 - py * a2, iz);
+      break;
+    }
+    case MMX_JC_DISTANCE: { // f = |x - origin| - d ; df/dx = (x - origin)^T / |x - origin|
+      const D3 diff = o.vp - gl;
+      const double nrm = sqrt(ddot(diff, diff));
+      o.f[0] = nrm - double(k.planeD[c]);
+      if (nrm > 0.0) {
+        setRow(o.dp, diff, 1.0 / nrm);
+      }
+      break;
+    }
     default: { // MMX_JC_NORMAL, normal_error_function.cpp:14-31
       const D3 dist = o.vp - gl;
       o.f[0] = ddot(o.vn, dist);
@@ -336,7 +361,7 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
     }
   }
   const double cw = double(k.weight[c]);
-  if (cw != 0.0 && k.fw > 0.f) { // :197-199 ; blocks with weight_ <= 0 are skipped (skeleton_solver_function.cpp:223-231)
+  if (!skip && cw != 0.0 && k.fw > 0.f) { // :197-199 ; blocks with weight_ <= 0 are skipped (skeleton_solver_function.cpp:223-231)
     const double sqr = o.f[0] * o.f[0] + o.f[1] * o.f[1] + o.f[2] * o.f[2];
     const double wgt = cw * double(k.fw);
     o.werr = wgt * dlossValue(k.loss, sqr); // :207

@@ -949,8 +949,10 @@ __device__ __forceinline__ void generalRowsGather(const float* js, const float* 
       addSlot(e);
     }
     gJ[row * gst + c] = acc[0];
-    if ((fl & 15) == 3) {
+    if ((fl & 15) >= 2) {
       gJ[(row + 1) * gst + c] = acc[1];
+    }
+    if ((fl & 15) == 3) {
       gJ[(row + 2) * gst + c] = acc[2];
     }
   }

@@ -870,8 +870,10 @@ __global__ void __launch_bounds__(256) jointBlocksKernel(
     }
     float* col = jb + size_t(p) * M + row;
     col[0] = acc[0];
-    if (nrows == 3) {
+    if (nrows >= 2) {
       col[1] = acc[1];
+    }
+    if (nrows == 3) {
       col[2] = acc[2];
     }
   }

@@ -4,7 +4,8 @@ Same class and argument names as the reference's binding (pymomentum/solver2/sol
 432-560 SkeletonSolverFunction, :656-740 options, :876-916 Solver / GaussNewtonSolver;
 solver2_error_functions.cpp:340-442 PositionErrorFunction, :1094-1200 OrientationErrorFunction,
 :263-283 ModelParametersErrorFunction; solver2_distance_error_functions.cpp:93-201 NormalErrorFunction,
-:430-530 PlaneErrorFunction; solver2_aim_axis_error_functions.cpp:57-282 Aim* / FixedAxis*), so a
+:430-530 PlaneErrorFunction; solver2_aim_axis_error_functions.cpp:57-282 Aim* / FixedAxis*; Projection- and
+DistanceErrorFunction after the reference's classes of those names, without citations: include/mmx.h), so a
 call site written against pymomentum.solver2 reads the same here.  Differences, all additive:
 
 * everything is BATCHED: `solve` takes model parameters [P] or [B, P]; constraint payloads
@@ -269,6 +270,61 @@ class NormalErrorFunction(_BlockErrorFunction):
         local_normal = np.asarray(local_normal, dtype=np.float32)
         self._add_many(parent, weight, name, local_point=np.zeros_like(local_normal) if local_point is None else local_point,
                        local_normal=local_normal, global_point=global_point)  # fmt: skip
+
+
+def _pad_uv(target):
+    """(u, v) -> (u, v, 0): the block's global payload has three floats per constraint."""
+    t = np.asarray(target, dtype=np.float32)
+    return np.concatenate([t, np.zeros(t.shape[:-1] + (1,), np.float32)], axis=-1)
+
+
+class ProjectionErrorFunction(_BlockErrorFunction):
+    """ProjectionErrorFunctionT: the point `offset` of joint `parent` seen through the 3 x 4 camera matrix
+    `projection` against the 2D target (u, v); constraints whose depth falls below `near_clip` are skipped
+    (include/mmx.h, MMX_JC_PROJECTION).  L2 loss only."""
+
+    TYPE = _abi.MMX_JC_PROJECTION
+    FIELDS = (("projection", 12), ("offset", 3), ("target", 3))
+    MAP = {"projection": "projection", "local_point": "offset", "global_": "target"}
+
+    def __init__(self, character, near_clip: float = 1.0, weight: float = 1.0):
+        super().__init__(character, 2.0, 1.0, weight)
+        self.near_clip = float(near_clip)
+
+    def block(self, B: int) -> JointBlock:
+        blk = super().block(B)
+        blk.near_clip = self.near_clip
+        return blk
+
+    def add_constraint(self, projection, parent, target, offset=None, weight: float = 1.0, name: str = "") -> None:
+        proj = np.asarray(projection, dtype=np.float32)
+        self._add(parent, weight, name, projection=proj.reshape(proj.shape[:-2] + (12,)),
+                  offset=np.zeros(3, np.float32) if offset is None else offset, target=_pad_uv(target))  # fmt: skip
+
+    def add_constraints(self, projection, parent, target, offset=None, weight=None, name=None) -> None:
+        proj = np.asarray(projection, dtype=np.float32)
+        target = _pad_uv(target)
+        self._add_many(parent, weight, name, projection=proj.reshape(proj.shape[:-2] + (12,)),
+                       offset=np.zeros_like(target) if offset is None else offset, target=target)  # fmt: skip
+
+
+class DistanceErrorFunction(_BlockErrorFunction):
+    """DistanceErrorFunctionT: the distance of the point `offset` of joint `parent` from `origin` pulled to
+    `target` (include/mmx.h, MMX_JC_DISTANCE).  L2 loss only."""
+
+    TYPE = _abi.MMX_JC_DISTANCE
+    FIELDS = (("origin", 3), ("target", 0), ("offset", 3))
+    MAP = {"local_point": "offset", "global_": "origin", "plane_d": "target"}
+
+    def __init__(self, character, weight: float = 1.0):
+        super().__init__(character, 2.0, 1.0, weight)
+
+    def add_constraint(self, origin, target, parent, offset=None, weight: float = 1.0, name: str = "") -> None:
+        self._add(parent, weight, name, origin=origin, target=target, offset=np.zeros(3, np.float32) if offset is None else offset)
+
+    def add_constraints(self, origin, target, parent, offset=None, weight=None, name=None) -> None:
+        origin = np.asarray(origin, dtype=np.float32)
+        self._add_many(parent, weight, name, origin=origin, target=target, offset=np.zeros_like(origin) if offset is None else offset)
 
 
 class LimitErrorFunction(SkeletonErrorFunction):
