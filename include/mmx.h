@@ -517,6 +517,26 @@ int32_t mmx_problem_set_instance_parents(
  *   MMX_ROUTE_EXPLICIT_JACOBIAN  dense J in HBM -> J^T J (matrix cores; VALU beyond 384 columns) -> Cholesky step; the route
  *                                for problems outside the tree kernels' scope, among them systems of 513 ... 2048 solved
  *                                parameters (kMaxModelParams, momentum/math/types.h:426-429: a rig cannot have more)
+ *   MMX_ROUTE_WAVE               one launch, ONE WAVEFRONT per instance (four instances per workgroup, no workgroup barrier in
+ *                                the iteration loop), the system in registers and a few KB of LDS: the route for small rigs.
+ *                                MMX_ROUTE_AUTO never picks it yet; it is taken only when pinned.  Scope (anything else, pinned,
+ *                                is MMX_ERR_UNSUPPORTED with a message that names the condition, before theta or any output is
+ *                                touched):
+ *                                  rig          <= MMX_WAVE_MAX_JOINTS joints, any tree shape, any parameter count, per-instance
+ *                                               offsets / pre-rotations (mmx_problem_set_instance_rig)
+ *                                  system       1 .. MMX_WAVE_MAX_SOLVED solved parameters after the enabled mask and the
+ *                                               structural-zero elimination (shared parameters and every dof kind included)
+ *                                  constraints  position + orientation blocks with the L2 loss, at most MMX_WAVE_MAX_UNITS
+ *                                               constraint vectors (positions + 3 x orientations), constraint / block / per-element
+ *                                               function weights (columns 0 and 1); NOT robust losses, further joint blocks,
+ *                                               ellipsoid or parameter limits, the model-parameter prior, per-instance parents
+ *                                  options      MMX_STEP_GN_FIXED_LAMBDA, every do_line_search rule, MMX_PRECISION_F32; NOT the
+ *                                               LM schedule, the trust region, MMX_PRECISION_F64 / AUTO / MIXED
+ *                                  outputs      final_error, iterations, status, error and parameter history;
+ *                                               mmx_problem_solve_diagnostics after such a solve answers MMX_ERR_UNSUPPORTED and
+ *                                               MMX_SOLVE_PRECISION_SUSPECT is never set
+ *                                Added without an ABI bump (one enum value, no struct grows): a library that predates the route
+ *                                answers mmx_problem_set_tuning with MMX_ERR_INVALID_ARGUMENT -- that is the feature probe.
  * The route does not change WHAT is computed (same algorithm, same refinement); results of different routes agree to
  * rounding (tests/test_gpu_weak_damping.py, tests/test_gpu_fuzz.py).
  */
@@ -524,6 +544,10 @@ int32_t mmx_problem_set_instance_parents(
 #define MMX_ROUTE_FUSED 1
 #define MMX_ROUTE_WIDE 2
 #define MMX_ROUTE_EXPLICIT_JACOBIAN 3
+#define MMX_ROUTE_WAVE 4
+#define MMX_WAVE_MAX_JOINTS 64
+#define MMX_WAVE_MAX_SOLVED 32
+#define MMX_WAVE_MAX_UNITS 192 /* keeps a wave's share of LDS under 16 KB at 64 joints */
 typedef struct mmx_tuning {
   int32_t route; /* MMX_ROUTE_* */
   int32_t max_refinement_steps; /* iterative-refinement steps a solve may take per iteration on top of the fp32 Cholesky

@@ -332,7 +332,11 @@ class GnOptions(C.Structure):
         )
 
 
-ROUTES = {"auto": 0, "fused": 1, "wide": 2, "explicit_jacobian": 3}  # MMX_ROUTE_*
+ROUTES = {"auto": 0, "fused": 1, "wide": 2, "explicit_jacobian": 3, "wave": 4}  # MMX_ROUTE_*
+# scope of the one-wavefront-per-instance route (MMX_WAVE_MAX_* in include/mmx.h)
+WAVE_MAX_JOINTS = 64
+WAVE_MAX_SOLVED = 32
+WAVE_MAX_UNITS = 192
 
 
 class Tuning(C.Structure):

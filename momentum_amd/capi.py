@@ -237,7 +237,7 @@ class RigHandle:
             pass
 
 
-# Route every Problem created from here on starts with ("auto" | "fused" | "wide" | "explicit_jacobian"): the parity tests
+# Route every Problem created from here on starts with ("auto" | "fused" | "wide" | "explicit_jacobian" | "wave"): the parity tests
 # set it (monkeypatch.setattr) to send whole test bodies through one route; Problem.set_route changes it per handle.
 # "prefer_wide" (sweeps: MMX_TEST_ROUTE=prefer_wide, tests/conftest.py): every solve tries the wide route first and falls
 # back to the library's own choice where the problem is outside the tree kernels' scope.
@@ -285,7 +285,8 @@ class Problem:
         except Exception:
             pass
 
-    # -- which kernels mmx_solve runs (mmx_tuning): "auto" | "fused" | "wide" | "explicit_jacobian"
+    # -- which kernels mmx_solve runs (mmx_tuning): "auto" | "fused" | "wide" | "explicit_jacobian" | "wave" (one wavefront per
+    # instance, small rigs: taken only when pinned, MMX_ERR_UNSUPPORTED outside its scope -- include/mmx.h)
     def set_route(self, route: str, max_refinement_steps: int = 0) -> None:
         # a caller that pins a route means it: the sweep default (MMX_TEST_ROUTE=prefer_wide) steps back for this handle
         # until the caller returns to "auto" (route-pinned tests then run what they name under a forced-route sweep)
@@ -296,7 +297,7 @@ class Problem:
         t = _abi.Tuning()
         t.route = _abi.ROUTES[route]
         t.max_refinement_steps = int(max_refinement_steps)  # 0 default (up to three), -1 none, 1..3
-        t.mixed_tolerance, t.mixed_max_cg = getattr(self, "_mixed", (0.0, 0))  # MMX_PRECISION_MIXED: 0 = defaults (1e-7, 12)
+        t.mixed_tolerance, t.mixed_max_cg = getattr(self, "_mixed", (0.0, 0))  # MMX_PRECISION_MIXED: 0 = defaults (3e-9, 12)
         self._route_args = (route, int(max_refinement_steps))
         _check(lib().mmx_problem_set_tuning(self._h, C.byref(t)))
 

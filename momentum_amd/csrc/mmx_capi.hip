@@ -1374,7 +1374,7 @@ int32_t mmx_problem_set_tuning(mmx_problem* pb, const mmx_tuning* tuning) {
   if (tuning == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "tuning is null");
   }
-  if (tuning->route < MMX_ROUTE_AUTO || tuning->route > MMX_ROUTE_EXPLICIT_JACOBIAN) {
+  if (tuning->route < MMX_ROUTE_AUTO || tuning->route > MMX_ROUTE_WAVE) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_tuning::route: unknown MMX_ROUTE_* value");
   }
   if (tuning->max_refinement_steps < -1 || tuning->max_refinement_steps > 3) {
@@ -2165,6 +2165,49 @@ static bool mixedUsable(const mmx_problem* pb, const mmx_gn_options* o) {
       mmx::fusedMixedUsable(pb->rig->J, pb->rig->P, pb->U, pb->fdev.nsrc, pb->fdev.n, pb->fdev.numCells);
 }
 
+// MMX_ROUTE_WAVE (mmx_wave.hip, scope table in include/mmx.h): null when the one-wavefront-per-instance solve takes this
+// problem with these options, else the condition it fails (the pinned route then answers MMX_ERR_UNSUPPORTED with it)
+static const char* waveRefusal(const mmx_problem* pb, const mmx_gn_options* o) {
+  const mmx::ProblemDev& d = pb->dev;
+  if (pb->rig->J > MMX_WAVE_MAX_JOINTS) {
+    return "MMX_ROUTE_WAVE: more than MMX_WAVE_MAX_JOINTS (64) joints";
+  }
+  if (pb->fdev.n > MMX_WAVE_MAX_SOLVED) {
+    return "MMX_ROUTE_WAVE: more than MMX_WAVE_MAX_SOLVED (32) solved parameters";
+  }
+  if (pb->fdev.n <= 0 || pb->U <= 0) {
+    return "MMX_ROUTE_WAVE: no solved parameter, or no position / orientation constraint";
+  }
+  if (pb->U > MMX_WAVE_MAX_UNITS) {
+    return "MMX_ROUTE_WAVE: more than MMX_WAVE_MAX_UNITS (192) constraint vectors (positions + 3 x orientations)";
+  }
+  if (d.lossPos.type != 0 || d.lossOri.type != 0) {
+    return "MMX_ROUTE_WAVE: robust losses are outside the route (L2 only)";
+  }
+  if (d.numBlocks > 0 || d.G > 0 || pb->fdev.GT > 0) {
+    return "MMX_ROUTE_WAVE: further joint-constraint blocks are outside the route";
+  }
+  if (d.NE > 0) {
+    return "MMX_ROUTE_WAVE: ellipsoid limits are outside the route";
+  }
+  if (d.NL > 0) {
+    return "MMX_ROUTE_WAVE: parameter limits are outside the route";
+  }
+  if (d.hasModel != 0 || d.M > d.rowsJoint) {
+    return "MMX_ROUTE_WAVE: the model-parameter prior is outside the route";
+  }
+  if (d.instPosParent != nullptr || d.instOriParent != nullptr) {
+    return "MMX_ROUTE_WAVE: per-instance constraint parents are outside the route";
+  }
+  if (o->step_rule != MMX_STEP_GN_FIXED_LAMBDA) {
+    return "MMX_ROUTE_WAVE: only MMX_STEP_GN_FIXED_LAMBDA (not the LM schedule, not the trust region)";
+  }
+  if (mmx::waveLdsBytes(pb->rig->J, pb->rig->P, pb->U, pb->fdev.n) > 160 * 1024) {
+    return "MMX_ROUTE_WAVE: the parameter vector does not fit a wave's share of LDS";
+  }
+  return nullptr;
+}
+
 static int32_t solveMixedImpl(
     mmx_problem* pb,
     const mmx_gn_options* o,
@@ -2285,6 +2328,9 @@ static int32_t solveImpl(
   if (theta_dev == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "options / theta is null");
   }
+  if (pb->tuning.route == MMX_ROUTE_WAVE) {
+    return fail(MMX_ERR_UNSUPPORTED, "MMX_ROUTE_WAVE: only MMX_PRECISION_F32 (not F64 / AUTO / MIXED)");
+  }
   const bool mixedOk = mixedUsable(pb, o);
   if (parameter_history != nullptr && !(o->precision == MMX_PRECISION_MIXED && mixedOk)) {
     return fail(MMX_ERR_UNSUPPORTED, "parameter_history is single precision's (MMX_PRECISION_F32) and the mixed-precision instantiation's: the double instantiation does not record it");
@@ -2384,6 +2430,43 @@ static int32_t solveF32Impl(
   // 154: 4.2e5 / 3.7e5, 166: 3.9e5 / 2.8e5, 183: 3.5e5 / 2.7e5, 219: 3.3e5 / 2.2e5) -- up to eight blocks (two or three
   // workgroups per CU) the fused solve stays.  mmx_tuning::route pins either.
   const int32_t route = pb->tuning.route;
+  if (route == MMX_ROUTE_WAVE) {
+    // one wavefront per instance, the whole SolverT::solve loop in one launch (small rigs; taken only when pinned)
+    if (const char* why = waveRefusal(pb, o)) {
+      return fail(MMX_ERR_UNSUPPORTED, why);
+    }
+    if (step_history != nullptr) {
+      return fail(MMX_ERR_UNSUPPORTED, "MMX_ROUTE_WAVE: step_history is the LM schedule's");
+    }
+    pb->lastRoute = MMX_ROUTE_WAVE;
+    pb->diagValid = false; // (no precision estimate on this route)
+    MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
+    MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
+    MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
+    mmx::SolveStateDev wst{};
+    wst.iterations = iterations != nullptr ? iterations : pb->sIters.as<int32_t>();
+    wst.status = status != nullptr ? status : pb->sStatus.as<int32_t>();
+    wst.finalError = final_error != nullptr ? final_error : pb->sFinalErr.as<double>();
+    wst.errorHistory = error_history;
+    wst.paramHistory = parameter_history;
+    if (error_history != nullptr && o->max_iterations > 0) {
+      MMX_HIP(mmx::zeroAsync(error_history, B * size_t(o->max_iterations) * sizeof(double), s));
+    }
+    if (parameter_history != nullptr && o->max_iterations > 0) {
+      MMX_HIP(mmx::zeroAsync(parameter_history, B * size_t(o->max_iterations) * P * sizeof(float), s));
+    }
+    mmx::FusedParams wp{};
+    wp.lambda = o->regularization;
+    wp.threshold = o->threshold;
+    wp.minIterations = o->min_iterations;
+    wp.maxIterations = o->max_iterations;
+    wp.refine = refineSteps(pb);
+    wp.doLineSearch = o->do_line_search;
+    wp.stepRule = o->step_rule;
+    MMX_ZONE("wave solve: all iterations in one launch, one wavefront per instance");
+    MMX_HIP(mmx::launchWaveSolve(pb->rigDev, pb->dev, pb->fdev, theta_dev, wst, wp, s));
+    return MMX_OK;
+  }
   const bool forceWide = route == MMX_ROUTE_WIDE;
   const bool trust = o->step_rule == MMX_STEP_TRUST_REGION;
   // (the trust region's re-solve loops live in the one-launch solve; the wide route drives them from the host, several

@@ -234,6 +234,13 @@ bool fusedMixedUsable(int J, int P, int U, int nsrc, int n, int numCells);
 hipError_t launchFusedMixed(
     const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, float* theta, const SolveStateDev& st, const FusedParams& fp, const MixSelect& sel, int blocks, long long* dbgClk, hipStream_t stream);
 
+// MMX_ROUTE_WAVE (mmx_wave.hip): one wavefront per instance, four instances per workgroup; position + orientation blocks with
+// the L2 loss, J <= MMX_WAVE_MAX_JOINTS, 1 <= fd.n <= MMX_WAVE_MAX_SOLVED, fd.U <= MMX_WAVE_MAX_UNITS, fixed-lambda Gauss-Newton
+// with or without backtracking (fp.stepRule is not read).  Kernel nodes only.  st: iterations, status, finalError and the two
+// histories are written; diag is not.
+size_t waveLdsBytes(int J, int P, int U, int n); // dynamic LDS of a workgroup
+hipError_t launchWaveSolve(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, float* theta, const SolveStateDev& st, const FusedParams& fp, hipStream_t stream);
+
 // double-precision solve (mmx_f64.hip)
 size_t solveF64LdsBytes(int J, int P, int U, int n, int G = 0, int genRows = 0);
 bool solveF64IsResident(int J, int P, int U, int n, int G = 0, int genRows = 0); // the system stays in LDS: no J / H scratch is read or written
@@ -265,7 +272,7 @@ hipError_t launchSolveF64(
     hipStream_t stream,
     const F64AssemblyList& list = F64AssemblyList{nullptr, nullptr, nullptr, 0},
     const F64Select& select = F64Select{nullptr, nullptr, nullptr, nullptr});
-// elements whose status has a bit of `mask` set, in index order: map[0 .. *count - 1]
+// elements whose status has a bit of `mask` set, in no particular order: map[0 .. *count - 1]
 hipError_t launchSelectSuspect(const int32_t* status, int B, int32_t mask, int32_t* map, int32_t* count, hipStream_t stream, int32_t require = 0);
 
 size_t fkJacobianLdsBytes(int J, int P, int U);

@@ -540,6 +540,17 @@ class Solver:
         self._history = None
         self._store_history = False
         self._iteration_history = {}
+        self._route = "auto"
+
+    def set_route(self, name: str):
+        """Pins the kernels the solve runs ("auto" | "fused" | "wide" | "explicit_jacobian" | "wave": capi.Problem.set_route);
+        forwarded to the lowered problem before every solve.  A pinned route the problem does not fit raises.  Returns self."""
+        from ._abi import ROUTES
+
+        if name not in ROUTES:
+            raise KeyError(name)
+        self._route = name
+        return self
 
     def set_store_history(self, b: bool) -> None:
         """SolverT::setStoreHistory (solver.h / solver.cpp:53-72)"""
@@ -568,6 +579,9 @@ class Solver:
         single, mp = fn._params(model_parameters)
         pb, torch = fn.lower(mp.shape[0])
         pb.set_enabled(self._enabled if self._enabled is not None else np.ones(fn.get_num_parameters(), np.uint8))
+        if self._route != "auto" or getattr(pb, "_solver_route", "auto") != "auto":
+            pb.set_route(self._route)
+            pb._solver_route = self._route
         o = self.options
         opt = GnOptions.make(min_iterations=o.min_iterations, max_iterations=o.max_iterations, threshold=o.threshold,
                              regularization=getattr(o, "regularization", 0.05), do_line_search=self._line_search_rule if getattr(o, "do_line_search", False) else 0)  # fmt: skip
