@@ -291,6 +291,8 @@ typedef struct mmx_ellipsoid_limit {
  *   MMX_JC_NORMAL             NormalErrorFunctionT normal_error_function.cpp:14-31              1  local_point, local_dir=localNormal (normalised), global=globalPoint
  *   MMX_JC_PROJECTION         ProjectionErrorFunctionT (see the note below)                     2  local_point=offset, projection=P, global=(u, v, ignored), near_clip
  *   MMX_JC_DISTANCE           DistanceErrorFunctionT   (see the note below)                     1  local_point=offset, global=origin, plane_d=target distance
+ *   MMX_JC_JOINT_TO_JOINT_DISTANCE  JointToJointDistanceErrorFunctionT (see the second note)    1  parent=[joints A | joints B], local_point=offset on A,
+ *                                                                                                  local_dir=offset on B (a point), plane_d=target distance
  * Vectors are normalised on ingest exactly where the reference's data constructors do
  * (plane_error_function.h:30, aim_error_function.h:34, fixed_axis_error_function.h:29-30,
  * normal_error_function.h:34).
@@ -307,6 +309,20 @@ typedef struct mmx_ellipsoid_limit {
  * target, parent, offset, weight) from memory of the reference, without a checkout at hand, so they carry no file:line
  * citations yet.  To confirm against the reference: the near-clip test p.z < nearClip and its default of 1; that neither
  * function applies a constant weight factor (like kPositionWeight); that neither takes a robust loss.
+ *
+ * The pair function (additive to ABI 12: no struct grows, the version stays), the first that ties two joints to each other
+ * instead of one joint to the world.  With x_a = T_A * offset_a and x_b = T_B * offset_b (each the point of a position constraint):
+ *   MMX_JC_JOINT_TO_JOINT_DISTANCE  f = |x_a - x_b| - d, df/dx_a = n^T, df/dx_b = -n^T with n = (x_a - x_b) / |x_a - x_b|
+ *                      (both zero where the norm is zero: the row is zero and the residual -sqrt(fw w) d, as for MMX_JC_DISTANCE).
+ *                      Row: sqrt(fw w) n^T (dx_a/dtheta - dx_b/dtheta); it walks the ancestor chains of BOTH joints and cancels
+ *                      on their common part.  Error fw * w * f^2.
+ *   `parent` holds 2 * count joints for this type alone: the `count` joints A, then the `count` joints B (A = B and A an
+ *   ancestor of B are legal).  `local_dir` is the offset on B, a point: it is NOT normalised on ingest.  `global`,
+ *   `projection` and `near_clip` are not read (`global` may be NULL).  L2 loss only, refused like the two types above.
+ * PROVENANCE: this restates momentum's JointToJointDistanceErrorFunctionT (constraint data: joint1, offset1, joint2, offset2,
+ * targetDistance, weight) from memory of the reference, without a checkout at hand, so it carries no file:line citations yet.
+ * To confirm against the reference: that the function applies no constant weight factor (like kPositionWeight); that it
+ * takes no robust loss; what it does at zero distance (here: zero row, residual -sqrt(fw w) d).
  */
 #define MMX_JC_PLANE 0
 #define MMX_JC_HALF_PLANE 1
@@ -318,16 +334,17 @@ typedef struct mmx_ellipsoid_limit {
 #define MMX_JC_NORMAL 7
 #define MMX_JC_PROJECTION 8 /* ABI 12 */
 #define MMX_JC_DISTANCE 9 /* ABI 12 */
+#define MMX_JC_JOINT_TO_JOINT_DISTANCE 10 /* additive to ABI 12: parent is [2 * count] */
 #define MMX_MAX_JOINT_BLOCKS 8
 
 typedef struct mmx_joint_constraint_block {
   int32_t type; /* MMX_JC_* */
   int32_t count; /* constraints per batch element */
-  const int32_t* parent; /* [count] HOST, batch-shared: ConstraintData::parent */
+  const int32_t* parent; /* [count] HOST, batch-shared: ConstraintData::parent (MMX_JC_JOINT_TO_JOINT_DISTANCE: [2 * count], joints A then joints B) */
   const float* local_point; /* [B][count][3] or NULL when the type has no point */
-  const float* local_dir; /* [B][count][3] or NULL when the type has no direction */
-  const float* global; /* [B][count][3] */
-  const float* plane_d; /* [B][count] (plane types; MMX_JC_DISTANCE: the target distance) */
+  const float* local_dir; /* [B][count][3] or NULL when the type has no direction (MMX_JC_JOINT_TO_JOINT_DISTANCE: the offset on joint B) */
+  const float* global; /* [B][count][3] (MMX_JC_JOINT_TO_JOINT_DISTANCE: not read, may be NULL) */
+  const float* plane_d; /* [B][count] (plane types; MMX_JC_DISTANCE / MMX_JC_JOINT_TO_JOINT_DISTANCE: the target distance) */
   const float* weight; /* [B][count] ConstraintData::weight */
   float function_weight; /* SkeletonErrorFunction::weight_ */
   float loss_alpha, loss_c; /* GeneralizedLossT(alpha, c); c <= 0: default L2, c = 1 */

@@ -284,6 +284,29 @@ struct NormalData {
   size_t parent = 0;
   float weight = 1.f;
 };
+// ABI 12's two point functions and the pair function (include/mmx.h: restated without file:line citations)
+struct ProjectionData {
+  std::array<float, 12> projection{{1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f}}; // 3 x 4 row-major camera matrix
+  Vector3f offset{0.f, 0.f, 0.f};
+  std::array<float, 2> target{{0.f, 0.f}}; // (u, v)
+  size_t parent = 0;
+  float weight = 1.f;
+};
+struct DistanceData {
+  Vector3f origin{0.f, 0.f, 0.f};
+  float target = 0.f; // target distance
+  Vector3f offset{0.f, 0.f, 0.f};
+  size_t parent = 0;
+  float weight = 1.f;
+};
+struct JointToJointDistanceData {
+  size_t joint1 = 0;
+  Vector3f offset1{0.f, 0.f, 0.f};
+  size_t joint2 = 0;
+  Vector3f offset2{0.f, 0.f, 0.f};
+  float targetDistance = 0.f;
+  float weight = 1.f;
+};
 enum class JointErrorFunctionType {
   Plane = MMX_JC_PLANE, // PlaneErrorFunction(above = false)
   HalfPlane = MMX_JC_HALF_PLANE, // PlaneErrorFunction(above = true)
@@ -292,7 +315,10 @@ enum class JointErrorFunctionType {
   FixedAxisDiff = MMX_JC_FIXED_AXIS_DIFF,
   FixedAxisCos = MMX_JC_FIXED_AXIS_COS,
   FixedAxisAngle = MMX_JC_FIXED_AXIS_ANGLE,
-  Normal = MMX_JC_NORMAL
+  Normal = MMX_JC_NORMAL,
+  Projection = MMX_JC_PROJECTION, // L2 loss only, like the next two
+  Distance = MMX_JC_DISTANCE,
+  JointToJointDistance = MMX_JC_JOINT_TO_JOINT_DISTANCE // added with addJointToJointDistanceErrorFunction (two parent lists)
 };
 
 // One SkeletonSolverFunction + PositionErrorFunction + OrientationErrorFunction per batch element.
@@ -462,24 +488,25 @@ class BatchedSkeletonSolverFunction {
     dirty_ = true;
   }
   // SkeletonSolverFunction::addErrorFunction for one of the further joint error functions
-  // (Plane / Aim / FixedAxis / Normal); parents are shared by the batch.  Returns the block's index.
+  // (Plane / Aim / FixedAxis / Normal / Projection / Distance); parents are shared by the batch.  Returns the block's index.
   size_t addJointErrorFunction(JointErrorFunctionType type, const std::vector<size_t>& parents, float lossAlpha = 2.f, float lossC = 1.f) {
-    if (blocks_.size() >= MMX_MAX_JOINT_BLOCKS) {
-      throw std::runtime_error("momentum_amd: too many joint error functions");
+    if (type == JointErrorFunctionType::JointToJointDistance) {
+      throw std::runtime_error("momentum_amd: a joint-to-joint distance function takes two parent lists (addJointToJointDistanceErrorFunction)");
     }
-    Block k;
-    k.type = int32_t(type);
-    k.parent.assign(parents.begin(), parents.end());
-    const size_t cnt = batch_ * parents.size();
-    k.localPoint.assign(3 * cnt, 0.f);
-    k.localDir.assign(3 * cnt, 0.f);
-    k.global.assign(3 * cnt, 0.f);
-    k.planeD.assign(cnt, 0.f);
-    k.weight.assign(cnt, 0.f); // constraints not set yet carry weight 0 (skipped, joint_error_function-inl.h:197-199)
-    k.loss[0] = lossAlpha, k.loss[1] = lossC;
-    blocks_.push_back(std::move(k));
+    return addBlock(type, parents, {}, lossAlpha, lossC);
+  }
+  // JointToJointDistanceErrorFunction: constraint i ties a point of joints1[i] to a point of joints2[i] (shared by the batch;
+  // the two may coincide or lie on one chain).  L2 loss only.
+  size_t addJointToJointDistanceErrorFunction(const std::vector<size_t>& joints1, const std::vector<size_t>& joints2) {
+    if (joints1.size() != joints2.size()) {
+      throw std::runtime_error("momentum_amd: joint-to-joint distance function with parent lists of different length");
+    }
+    return addBlock(JointErrorFunctionType::JointToJointDistance, joints1, joints2, 2.f, 1.f);
+  }
+  // ProjectionErrorFunction's nearClip (constraints whose depth falls below it are skipped)
+  void setNearClip(size_t block, float nearClip) {
+    blockAt(block).nearClip = nearClip;
     dirty_ = true;
-    return blocks_.size() - 1;
   }
   void setWeight(size_t block, float weight) { // SkeletonErrorFunction::setWeight of that error function
     blockAt(block).fw = weight;
@@ -507,6 +534,31 @@ class BatchedSkeletonSolverFunction {
     Block& k = expect(block, b, c.size(), MMX_JC_NORMAL, MMX_JC_NORMAL);
     for (size_t i = 0; i < c.size(); ++i) {
       put(k, b, i, c[i].localPoint.data(), c[i].localNormal.data(), c[i].globalPoint.data(), 0.f, c[i].weight);
+    }
+  }
+  void setConstraints(size_t block, size_t b, const std::vector<ProjectionData>& c) {
+    Block& k = expect(block, b, c.size(), MMX_JC_PROJECTION, MMX_JC_PROJECTION);
+    for (size_t i = 0; i < c.size(); ++i) {
+      const float uv[3] = {c[i].target[0], c[i].target[1], 0.f};
+      put(k, b, i, c[i].offset.data(), nullptr, uv, 0.f, c[i].weight);
+      std::copy(c[i].projection.begin(), c[i].projection.end(), k.projection.begin() + 12 * (b * k.parent.size() + i));
+    }
+  }
+  void setConstraints(size_t block, size_t b, const std::vector<DistanceData>& c) {
+    Block& k = expect(block, b, c.size(), MMX_JC_DISTANCE, MMX_JC_DISTANCE);
+    for (size_t i = 0; i < c.size(); ++i) {
+      put(k, b, i, c[i].offset.data(), nullptr, c[i].origin.data(), c[i].target, c[i].weight);
+    }
+  }
+  // (the joints of the data must be the lists the function was added with: parents are shared by the batch)
+  void setConstraints(size_t block, size_t b, const std::vector<JointToJointDistanceData>& c) {
+    Block& k = expect(block, b, c.size(), MMX_JC_JOINT_TO_JOINT_DISTANCE, MMX_JC_JOINT_TO_JOINT_DISTANCE);
+    const float none[3] = {0.f, 0.f, 0.f};
+    for (size_t i = 0; i < c.size(); ++i) {
+      if (int32_t(c[i].joint1) != k.parent[i] || int32_t(c[i].joint2) != k.parentB[i]) {
+        throw std::runtime_error("momentum_amd: joint-to-joint distance data names other joints than its error function");
+      }
+      put(k, b, i, c[i].offset1.data(), c[i].offset2.data(), none, c[i].targetDistance, c[i].weight);
     }
   }
   void setEnabledParameters(const ParameterSet& ps) {
@@ -540,11 +592,19 @@ class BatchedSkeletonSolverFunction {
     d.pos_loss_alpha = lossPos_[0], d.pos_loss_c = lossPos_[1];
     d.ori_loss_alpha = lossOri_[0], d.ori_loss_c = lossOri_[1];
     std::vector<mmx_joint_constraint_block> jb(blocks_.size());
+    std::vector<std::vector<int32_t>> pairParents(blocks_.size()); // [joints A | joints B] of the pair blocks
     for (size_t i = 0; i < blocks_.size(); ++i) {
       const Block& k = blocks_[i];
       jb[i].type = k.type;
       jb[i].count = int32_t(k.parent.size());
       jb[i].parent = k.parent.data();
+      if (k.type == MMX_JC_JOINT_TO_JOINT_DISTANCE) {
+        pairParents[i] = k.parent;
+        pairParents[i].insert(pairParents[i].end(), k.parentB.begin(), k.parentB.end());
+        jb[i].parent = pairParents[i].data();
+      }
+      jb[i].projection = k.type == MMX_JC_PROJECTION ? k.projection.data() : nullptr;
+      jb[i].near_clip = k.nearClip;
       jb[i].local_point = k.localPoint.data();
       jb[i].local_dir = k.localDir.data();
       jb[i].global = k.global.data();
@@ -597,10 +657,35 @@ class BatchedSkeletonSolverFunction {
   struct Block {
     int32_t type = 0;
     std::vector<int32_t> parent;
+    std::vector<int32_t> parentB; // JointToJointDistance: the second joint of every constraint
     std::vector<float> localPoint, localDir, global, planeD, weight;
+    std::vector<float> projection; // Projection: [batch][count][12]
+    float nearClip = 1.f;
     float fw = 1.f;
     float loss[2] = {2.f, 1.f};
   };
+  size_t addBlock(JointErrorFunctionType type, const std::vector<size_t>& parents, const std::vector<size_t>& parentsB, float lossAlpha, float lossC) {
+    if (blocks_.size() >= MMX_MAX_JOINT_BLOCKS) {
+      throw std::runtime_error("momentum_amd: too many joint error functions");
+    }
+    Block k;
+    k.type = int32_t(type);
+    k.parent.assign(parents.begin(), parents.end());
+    k.parentB.assign(parentsB.begin(), parentsB.end());
+    const size_t cnt = batch_ * parents.size();
+    if (type == JointErrorFunctionType::Projection) {
+      k.projection.assign(12 * cnt, 0.f);
+    }
+    k.localPoint.assign(3 * cnt, 0.f);
+    k.localDir.assign(3 * cnt, 0.f);
+    k.global.assign(3 * cnt, 0.f);
+    k.planeD.assign(cnt, 0.f);
+    k.weight.assign(cnt, 0.f); // constraints not set yet carry weight 0 (skipped, joint_error_function-inl.h:197-199)
+    k.loss[0] = lossAlpha, k.loss[1] = lossC;
+    blocks_.push_back(std::move(k));
+    dirty_ = true;
+    return blocks_.size() - 1;
+  }
   Block& blockAt(size_t block) {
     if (block >= blocks_.size()) {
       throw std::runtime_error("momentum_amd: joint error function index out of range");

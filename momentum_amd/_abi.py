@@ -142,6 +142,7 @@ def ellipsoid_array(items):
 MMX_JC_PLANE, MMX_JC_HALF_PLANE, MMX_JC_AIM_DIST, MMX_JC_AIM_DIR = 0, 1, 2, 3
 MMX_JC_FIXED_AXIS_DIFF, MMX_JC_FIXED_AXIS_COS, MMX_JC_FIXED_AXIS_ANGLE, MMX_JC_NORMAL = 4, 5, 6, 7
 MMX_JC_PROJECTION, MMX_JC_DISTANCE = 8, 9  # ABI 12
+MMX_JC_JOINT_TO_JOINT_DISTANCE = 10  # additive to ABI 12: the block's parent array holds the joints A, then the joints B
 MMX_MAX_JOINT_BLOCKS = 8
 
 
@@ -175,17 +176,24 @@ class JointConstraintBlock(C.Structure):
 
 class JointBlock:
     """Python-side description of one further joint-constraint block (Plane / Aim / FixedAxis /
-    Normal / Projection / Distance error function).  Payload arrays are numpy ([K,..] for one instance or
-    [B,K,..]) or, for the device path, contiguous float32 cuda tensors [B,K,..].  `projection` holds the
-    projection block's 3 x 4 row-major camera matrices (12 floats per constraint)."""
+    Normal / Projection / Distance / JointToJointDistance error function).  Payload arrays are numpy ([K,..] for one
+    instance or [B,K,..]) or, for the device path, contiguous float32 cuda tensors [B,K,..].  `projection` holds the
+    projection block's 3 x 4 row-major camera matrices (12 floats per constraint).  `parent_b` ([K], the pair
+    type only) is the second joint of every constraint; for that type `local_dir` is the offset on it (a point),
+    `plane_d` the target distance and `global_` may be None."""
 
     FIELDS = (("local_point", 3), ("local_dir", 3), ("global_", 3), ("plane_d", 0), ("weight", 0), ("projection", 12))
 
     def __init__(self, type, parent, weight, global_, local_point=None, local_dir=None, plane_d=None,
-                 function_weight: float = 1.0, loss=(2.0, 1.0), projection=None, near_clip: float = 1.0):  # fmt: skip
+                 function_weight: float = 1.0, loss=(2.0, 1.0), projection=None, near_clip: float = 1.0, parent_b=None):  # fmt: skip
         self.type = int(type)
         self.parent = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
         self.count = int(self.parent.shape[0])
+        self.parent_b = None if parent_b is None else np.ascontiguousarray(parent_b, dtype=np.int32).reshape(-1)
+        if (self.type == MMX_JC_JOINT_TO_JOINT_DISTANCE) != (self.parent_b is not None):
+            raise ValueError("parent_b goes with MMX_JC_JOINT_TO_JOINT_DISTANCE blocks, and only with them")
+        if self.parent_b is not None and self.parent_b.shape[0] != self.count:
+            raise ValueError(f"parent_b has {self.parent_b.shape[0]} joints for {self.count} constraints")
         self.weight, self.global_ = weight, global_
         self.local_point, self.local_dir, self.plane_d = local_point, local_dir, plane_d
         self.function_weight = float(function_weight)
@@ -207,7 +215,11 @@ class JointBlock:
 
         return JointBlock(self.type, self.parent, cut(self.weight, 0), cut(self.global_, 3), cut(self.local_point, 3),
                           cut(self.local_dir, 3), cut(self.plane_d, 0), self.function_weight, self.loss,
-                          cut(self.projection, 12), self.near_clip)  # fmt: skip
+                          cut(self.projection, 12), self.near_clip, self.parent_b)  # fmt: skip
+
+    def parent_array(self) -> np.ndarray:
+        """What the C side reads as `parent`: [count], or [2 * count] (joints A, then joints B) for the pair type."""
+        return self.parent if self.parent_b is None else np.ascontiguousarray(np.concatenate([self.parent, self.parent_b]))
 
     def struct(self, keep: list, batch=None, device: bool = False) -> JointConstraintBlock:
         """ctypes struct; arrays it points to are appended to `keep`.  batch = B checks [B,K,..] shapes."""
@@ -228,9 +240,10 @@ class JointBlock:
                     x = x.reshape((batch, self.count, d) if d else (batch, self.count))
                 keep.append(x)
                 ptrs[name] = C.c_void_p(x.ctypes.data if x.size else 0)
-        keep.append(self.parent)
+        parents = self.parent_array()
+        keep.append(parents)
         return JointConstraintBlock(
-            self.type, self.count, C.c_void_p(self.parent.ctypes.data if self.count else 0), ptrs["local_point"], ptrs["local_dir"],
+            self.type, self.count, C.c_void_p(parents.ctypes.data if self.count else 0), ptrs["local_point"], ptrs["local_dir"],
             ptrs["global_"], ptrs["plane_d"], ptrs["weight"], self.function_weight, self.loss[0], self.loss[1],
             ptrs["projection"], self.near_clip,
         )  # fmt: skip

@@ -333,7 +333,8 @@ class Problem:
         joint_blocks: list of _abi.JointBlock (Plane / Aim / FixedAxis / Normal / Projection / Distance error
         functions), payload of the same memory kind as the constraint arrays; their rows follow the orientation rows
         (two per projection constraint: its `projection` holds 12 floats per constraint, `near_clip` the depth below
-        which a constraint is skipped; L2 loss only for projection and distance blocks).
+        which a constraint is skipped; L2 loss only for projection and distance blocks; a joint-to-joint distance block
+        names its second joints in `parent_b`, its second offsets in `local_dir`, and has no `global_`).
         function_weights: [B, C] per-element error-function weights (errorFunctionWeights of solveTensorIKProblem), columns
         position, orientation, limits, model parameters, joint block 0, ...; same memory kind as the constraint arrays."""
         import torch

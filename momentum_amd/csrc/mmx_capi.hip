@@ -195,6 +195,7 @@ struct mmx_problem {
   struct JointBlockHost {
     int32_t type = 0, count = 0;
     std::vector<int32_t> parent;
+    std::vector<int32_t> parentB; // MMX_JC_JOINT_TO_JOINT_DISTANCE: the second joint of every constraint, else empty
     DevBuf oLocalPoint, oLocalDir, oGlobal, oPlaneD, oWeight, oProjection; // owned copies of a host payload
   };
   std::vector<std::unique_ptr<JointBlockHost>> blocks;
@@ -296,20 +297,28 @@ int32_t uploadProblemTables(mmx_problem* pb) {
   MMX_HIP(upload(pb->dJointTin, t.tin));
   pb->dev.jointTin = pb->dJointTin.as<int32_t>();
   {
-    std::vector<int32_t> gj, gt, gb;
+    // flattened constraints [G], then [G] second joints: the B joint of a pair constraint, -1 for every other type
+    std::vector<int32_t> gj, gt, gb, gj2, gt2;
     for (size_t i = 0; i < pb->blocks.size(); ++i) {
-      for (int32_t j : pb->blocks[i]->parent) {
+      const mmx_problem::JointBlockHost& h = *pb->blocks[i];
+      for (size_t c = 0; c < h.parent.size(); ++c) {
+        const int32_t j = h.parent[c], j2 = h.parentB.empty() ? -1 : h.parentB[c];
         gj.push_back(j);
         gt.push_back(t.tin[size_t(j)]);
         gb.push_back(int32_t(i));
+        gj2.push_back(j2);
+        gt2.push_back(j2 < 0 ? -1 : t.tin[size_t(j2)]);
       }
     }
+    const size_t G = gb.size();
+    gj.insert(gj.end(), gj2.begin(), gj2.end());
+    gt.insert(gt.end(), gt2.begin(), gt2.end());
     MMX_HIP(upload(pb->dGenJoint, gj));
     MMX_HIP(upload(pb->dGenTin, gt));
     MMX_HIP(upload(pb->dGenBlock, gb));
     MMX_HIP(upload(pb->dBlocks, pb->blockDev));
     pb->dev.numBlocks = int32_t(pb->blocks.size());
-    pb->dev.G = int32_t(gj.size());
+    pb->dev.G = int32_t(G);
     pb->dev.blocks = pb->dBlocks.as<mmx::JointBlockDev>();
     pb->dev.genJoint = pb->dGenJoint.as<int32_t>();
     pb->dev.genTin = pb->dGenTin.as<int32_t>();
@@ -373,7 +382,7 @@ int32_t uploadProblemTables(mmx_problem* pb) {
       }
     }
     // joints that carry a further joint error function or an ellipsoid limit count like constrained joints for the
-    // structure (solve list, source slots): point-like ones (projection and distance among them) see every dof above them,
+    // structure (solve list, source slots): point-like ones (projection, distance and BOTH joints of a pair among them) see every dof above them,
     // fixed-axis ones rotations only
     std::vector<int32_t> structPos, structOri;
     if (pb->instPos) {
@@ -387,6 +396,7 @@ int32_t uploadProblemTables(mmx_problem* pb) {
       for (int32_t j : h->parent) {
         (fixedAxis ? structOri : structPos).push_back(j);
       }
+      structPos.insert(structPos.end(), h->parentB.begin(), h->parentB.end()); // a pair row also walks the chain above its second point
     }
     for (const mmx_ellipsoid_limit& e : pb->ellipsoids) {
       structPos.push_back(e.parent);
@@ -752,6 +762,9 @@ int32_t uploadProblemTables(mmx_problem* pb) {
       const bool fixedAxis = h->type == MMX_JC_FIXED_AXIS_DIFF || h->type == MMX_JC_FIXED_AXIS_COS || h->type == MMX_JC_FIXED_AXIS_ANGLE;
       for (int32_t j : h->parent) {
         mark(j, !fixedAxis);
+      }
+      for (int32_t j : h->parentB) {
+        mark(j, true);
       }
     }
     for (const mmx_ellipsoid_limit& e : pb->ellipsoids) {
@@ -1670,29 +1683,31 @@ int32_t mmx_problem_set_constraints(mmx_problem* pb, const mmx_constraint_data* 
   for (int32_t i = 0; i < c->num_joint_blocks; ++i) {
     const mmx_joint_constraint_block& jb = c->joint_blocks[i];
     const std::string tag = "joint block " + std::to_string(i);
-    if (jb.type < MMX_JC_PLANE || jb.type > MMX_JC_DISTANCE) {
+    if (jb.type < MMX_JC_PLANE || jb.type > MMX_JC_JOINT_TO_JOINT_DISTANCE) {
       return fail(MMX_ERR_UNSUPPORTED, tag + ": unknown error-function type");
     }
     const bool pointOnly = jb.type == MMX_JC_PROJECTION || jb.type == MMX_JC_DISTANCE; // (ABI 12)
-    if (pointOnly && jb.loss_c > 0.f && !(jb.loss_alpha == 2.f && jb.loss_c == 1.f)) {
-      return fail(MMX_ERR_UNSUPPORTED, tag + ": projection / distance blocks take the L2 loss only (loss_c <= 0 or (alpha, c) = (2, 1))");
+    const bool pairType = jb.type == MMX_JC_JOINT_TO_JOINT_DISTANCE; // two points: parent is [2 * count], local_dir the second offset
+    if ((pointOnly || pairType) && jb.loss_c > 0.f && !(jb.loss_alpha == 2.f && jb.loss_c == 1.f)) {
+      return fail(MMX_ERR_UNSUPPORTED, tag + ": projection / distance / joint-to-joint distance blocks take the L2 loss only (loss_c <= 0 or (alpha, c) = (2, 1))");
     }
     if (jb.type == MMX_JC_PROJECTION && !std::isfinite(jb.near_clip)) {
       return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": near_clip is not finite");
     }
-    if (jb.count < 0 || (jb.count > 0 && (jb.parent == nullptr || jb.global == nullptr || jb.weight == nullptr))) {
+    if (jb.count < 0 || (jb.count > 0 && (jb.parent == nullptr || (!pairType && jb.global == nullptr) || jb.weight == nullptr))) {
       return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": negative count or null parent / global / weight array");
     }
     const bool plane = jb.type == MMX_JC_PLANE || jb.type == MMX_JC_HALF_PLANE;
     const bool fixedAxis = jb.type == MMX_JC_FIXED_AXIS_DIFF || jb.type == MMX_JC_FIXED_AXIS_COS || jb.type == MMX_JC_FIXED_AXIS_ANGLE;
-    const bool needD = plane || jb.type == MMX_JC_DISTANCE;
+    const bool needD = plane || jb.type == MMX_JC_DISTANCE || pairType;
     if (jb.count > 0 && ((!fixedAxis && jb.local_point == nullptr) || (!plane && !pointOnly && jb.local_dir == nullptr) || (needD && jb.plane_d == nullptr))) {
       return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": a payload array its error function needs is null");
     }
     if (jb.count > 0 && jb.type == MMX_JC_PROJECTION && jb.projection == nullptr) {
       return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": projection block without its projection matrices");
     }
-    for (int32_t k = 0; k < jb.count; ++k) {
+    const int32_t numParents = pairType ? 2 * jb.count : jb.count;
+    for (int32_t k = 0; k < numParents; ++k) {
       if (jb.parent[k] < 0 || jb.parent[k] >= pb->rig->J) {
         return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": parent joint out of range"); // MT_CHECK joint_error_function-inl.h:230
       }
@@ -1701,7 +1716,8 @@ int32_t mmx_problem_set_constraints(mmx_problem* pb, const mmx_constraint_data* 
     genCount += jb.count;
     if (!blocksChanged) {
       const mmx_problem::JointBlockHost& h = *pb->blocks[size_t(i)];
-      blocksChanged = h.type != jb.type || h.count != jb.count || !std::equal(h.parent.begin(), h.parent.end(), jb.parent);
+      blocksChanged = h.type != jb.type || h.count != jb.count || !std::equal(h.parent.begin(), h.parent.end(), jb.parent) ||
+          h.parentB.size() != size_t(numParents - jb.count) || !std::equal(h.parentB.begin(), h.parentB.end(), jb.parent + jb.count);
     }
   }
   if (genCount > 1024) {
@@ -1772,6 +1788,9 @@ int32_t mmx_problem_set_constraints(mmx_problem* pb, const mmx_constraint_data* 
       h->type = c->joint_blocks[i].type;
       h->count = c->joint_blocks[i].count;
       h->parent.assign(c->joint_blocks[i].parent, c->joint_blocks[i].parent + h->count);
+      if (h->type == MMX_JC_JOINT_TO_JOINT_DISTANCE) {
+        h->parentB.assign(c->joint_blocks[i].parent + h->count, c->joint_blocks[i].parent + 2 * h->count);
+      }
       pb->blocks.push_back(std::move(h));
     }
   }

@@ -241,14 +241,15 @@ struct LimitDev {
 };
 
 // == mmx_joint_constraint_block (include/mmx.h) for the device: one further JointErrorFunctionT
-// specialisation (Plane / Aim / FixedAxis / Normal / Projection / Distance) with `count` constraints per instance
+// specialisation (Plane / Aim / FixedAxis / Normal / Projection / Distance / JointToJointDistance) with `count`
+// constraints per instance
 struct JointBlockDev {
   int32_t type, count;
   int32_t first; // index of the block's first constraint in the flattened list (genJoint, genTin, genBlock)
   int32_t rowStart; // first row of the block in J / r
   const float* localPoint; // [B][count][3] or null
-  const float* localDir; // [B][count][3] or null
-  const float* global; // [B][count][3]
+  const float* localDir; // [B][count][3] or null (MMX_JC_JOINT_TO_JOINT_DISTANCE: the offset on the second joint, a point)
+  const float* global; // [B][count][3] (MMX_JC_JOINT_TO_JOINT_DISTANCE: not read, may be null)
   const float* planeD; // [B][count] or null
   const float* weight; // [B][count]
   float fw; // SkeletonErrorFunction::weight_
@@ -290,8 +291,8 @@ struct ProblemDev {
   // ---- further joint-constraint blocks (rows 3 U .. rowsJoint-1), explicit-Jacobian path only
   int32_t numBlocks, G; // blocks, constraints of all blocks
   const JointBlockDev* blocks; // [numBlocks]
-  const int32_t* genJoint; // [G] parent joint
-  const int32_t* genTin; // [G] tin[genJoint]
+  const int32_t* genJoint; // [2 G] parent joint; [G + g]: the second joint of a pair constraint (MMX_JC_JOINT_TO_JOINT_DISTANCE), else -1
+  const int32_t* genTin; // [2 G] tin[genJoint] (-1 where genJoint is)
   const int32_t* genBlock; // [G] block of the constraint
   // ---- LimitType::Ellipsoid entries of the limit block: rows 3 U + block rows .. rowsJoint-1, three each
   int32_t NE;
@@ -331,6 +332,13 @@ __device__ __forceinline__ JointBlockDev jointBlockOf(const ProblemDev& pb, int 
     k.fw *= pb.fnWeights[size_t(b) * size_t(pb.fnCols) + size_t(4 + i)];
   }
   return k;
+}
+// the second joint of flattened constraint g (pair constraints only, -1 for every other type) and its DFS position
+__device__ __forceinline__ int jointBlockSecondJoint(const ProblemDev& pb, const JointBlockDev& k, int g) {
+  return k.type == MMX_JC_JOINT_TO_JOINT_DISTANCE ? pb.genJoint[pb.G + g] : -1;
+}
+__device__ __forceinline__ int jointBlockSecondTin(const ProblemDev& pb, const JointBlockDev& k, int g) {
+  return k.type == MMX_JC_JOINT_TO_JOINT_DISTANCE ? pb.genTin[pb.G + g] : -1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -713,11 +721,34 @@ __device__ __forceinline__ F3 sourceDerivative(const ColumnSourceDev& s, const f
   return kLn2 * (un.v - F3{a[0], a[1], a[2]}); // scale: (v - t_a) * ln2
 }
 
+// d(x_a - x_b)/d(joint-parameter row (joint, dof)) of a pair constraint: the row of a source that is an ancestor-or-self of
+// the first point's joint (ancA), of the second's (ancB) or of both.  Every dof's derivative is linear in the point, so the
+// two chains are folded BEFORE the formula: rotation axis x (x_a - t) - axis x (x_b - t), translation the parent's linear
+// column once per chain, scale ln2 (x - t) per chain.  Above both joints the translation cancels to an exact zero and the
+// other two see x_a - x_b only.  transCol: that translation column (callers differ in how they look it up).
+template <typename TransColFn>
+__device__ __forceinline__ F3 pairSourceDerivative(const float* js, int joint, int dof, bool ancA, bool ancB, const F3& xa, const F3& xb, TransColFn transCol) {
+  const float sa = ancA ? 1.f : 0.f, sb = ancB ? 1.f : 0.f;
+  if (dof < 3) {
+    return (sa - sb) * transCol();
+  }
+  const float* a = js + kJs * joint;
+  const F3 t{a[0], a[1], a[2]};
+  const F3 off = sa * (xa - t) - sb * (xb - t);
+  if (dof < 6) {
+    const float* ax = a + 8 + 3 * (dof - 3);
+    return cross(F3{ax[0], ax[1], ax[2]}, off);
+  }
+  return kLn2 * off;
+}
+
 // ---------------------------------------------------------------------------------------------
 // evalFunction of the further JointErrorFunctionT specialisations + the weighting of
 // JointErrorFunctionT::getJacobian (joint_error_function-inl.h:197-226): one constraint with up to
 // one point v_p (NumPos) and one direction v_n, FuncDim = nrows in {1, 2, 3}, df/dv_p = dp, df/dv_n = dn
 // (row-major, rows >= nrows zero).
+// MMX_JC_JOINT_TO_JOINT_DISTANCE (pairPoint): v_n is a second POINT, on joint `joint2`, with its own ancestor chain; its
+// derivative dn = -dp, so the gather needs dp only (pairSourceDerivative).
 // ---------------------------------------------------------------------------------------------
 struct JointEval {
   F3 vp, vn;
@@ -726,8 +757,13 @@ struct JointEval {
   float sigma; // derivScale = sqrt(w * loss'(|f|^2)) ; 0 when the rows stay zero
   float werr; // w * loss(|f|^2)
   int nrows;
-  bool hasPoint, hasDir;
+  bool hasPoint, hasDir, pairPoint;
 };
+// flag word of a constraint record: rows | 16: point | 32: second vector | 64: the second vector is a point with its own
+// DFS position (stored where the ellipsoid records keep tinStop)
+__device__ __forceinline__ int jointEvalFlags(const JointEval& o) {
+  return o.nrows | (o.hasPoint ? 16 : 0) | (o.hasDir ? 32 : 0) | (o.pairPoint ? 64 : 0);
+}
 
 __device__ __forceinline__ F3 normalizedOrSame(const F3& a) { // Eigen normalized(): unchanged when the norm is zero
   const float n2 = dot(a, a);
@@ -739,7 +775,7 @@ __host__ __device__ __forceinline__ int jointBlockFuncDim(int type) {
   return (type == MMX_JC_AIM_DIST || type == MMX_JC_AIM_DIR || type == MMX_JC_FIXED_AXIS_DIFF) ? 3 : type == MMX_JC_PROJECTION ? 2 : 1;
 }
 
-__device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k, const float* js, int joint, size_t c) {
+__device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k, const float* js, int joint, int joint2, size_t c) {
   JointEval o;
   o.vp = o.vn = F3{0.f, 0.f, 0.f};
 #pragma unroll
@@ -751,6 +787,7 @@ __device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k,
   o.nrows = jointBlockFuncDim(k.type);
   o.hasPoint = k.type != MMX_JC_FIXED_AXIS_DIFF && k.type != MMX_JC_FIXED_AXIS_COS && k.type != MMX_JC_FIXED_AXIS_ANGLE;
   o.hasDir = k.type != MMX_JC_PLANE && k.type != MMX_JC_HALF_PLANE && k.type != MMX_JC_PROJECTION && k.type != MMX_JC_DISTANCE;
+  o.pairPoint = k.type == MMX_JC_JOINT_TO_JOINT_DISTANCE;
   bool skip = false; // a projection behind the near plane: no error, rows zero
   const float* w = js + kJs * joint;
   const F3 t{w[0], w[1], w[2]};
@@ -763,11 +800,14 @@ __device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k,
     m[3] += sc * a.y * b.x, m[4] += sc * a.y * b.y, m[5] += sc * a.y * b.z;
     m[6] += sc * a.z * b.x, m[7] += sc * a.z * b.y, m[8] += sc * a.z * b.z;
   };
-  const F3 gl = vec(k.global);
+  const F3 gl = o.pairPoint ? F3{0.f, 0.f, 0.f} : vec(k.global); // (the pair type has no world-space payload)
   if (o.hasPoint) {
     o.vp = t + qrot(q, s * vec(k.localPoint)); // state.transform * point
   }
-  if (o.hasDir) {
+  if (o.pairPoint) {
+    const float* w2 = js + kJs * joint2;
+    o.vn = F3{w2[0], w2[1], w2[2]} + qrot(Q4{w2[3], w2[4], w2[5], w2[6]}, w2[7] * vec(k.localDir)); // the second joint's transform * its point
+  } else if (o.hasDir) {
     o.vn = qrot(q, normalizedOrSame(vec(k.localDir))); // state.rotation() * dir, normalised by the data ctor
   }
   switch (k.type) {
@@ -853,6 +893,18 @@ __device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k,
       o.f[0] = nrm - k.planeD[c];
       if (nrm > 0.f) {
         setRow(o.dp, diff, 1.f / nrm);
+      }
+      break;
+    }
+    case MMX_JC_JOINT_TO_JOINT_DISTANCE: { // f = |x_a - x_b| - d ; df/dx_a = n^T = -df/dx_b, n = (x_a - x_b) / |x_a - x_b|
+      // (two points of ONE joint: x_a - x_b = s R (o_a - o_b) without the detour through the world positions, so equal
+      // offsets give an exact zero whatever the compiler fuses in the two transforms)
+      const F3 diff = joint2 == joint ? qrot(q, s * (vec(k.localPoint) - vec(k.localDir))) : o.vp - o.vn;
+      const float nrm = sqrtf(dot(diff, diff));
+      o.f[0] = nrm - k.planeD[c];
+      if (nrm > 0.f) {
+        setRow(o.dp, diff, 1.f / nrm);
+        setRow(o.dn, diff, -1.f / nrm);
       }
       break;
     }

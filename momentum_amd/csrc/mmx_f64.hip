@@ -219,7 +219,7 @@ __device__ double paramRowsErrorF64(const RigDev& rig, const ProblemDev& pb, con
 
 // SkeletonSolverFunctionT<double>::getError (skeleton_solver_function.cpp:64-83; rounded through float, :82)
 // The further JointErrorFunctionT<double> specialisations (Plane / HalfPlane, AimDist / AimDir, FixedAxisDiff / Cos /
-// Angle, Normal, Projection, Distance): evalFunction + the weighting of getJacobian in double -- evalJointConstraint of mmx_device.hpp with T =
+// Angle, Normal, Projection, Distance, JointToJointDistance): evalFunction + the weighting of getJacobian in double -- evalJointConstraint of mmx_device.hpp with T =
 // double (the constraint data stay float like the reference's tensors; joint_error_function-inl.h:197-226).
 struct JointEvalD {
   D3 vp, vn;
@@ -227,16 +227,16 @@ struct JointEvalD {
   double f[3];
   double sigma, werr;
   int nrows;
-  bool hasPoint, hasDir;
+  bool hasPoint, hasDir, pairPoint; // pairPoint: vn is a second point on joint2 (MMX_JC_JOINT_TO_JOINT_DISTANCE), dn = -dp
 };
-constexpr int kGevD = 26; // doubles per constraint in LDS: vp(3) vn(3) sigma dp(9) sigma dn(9) | tin, row | flags, -
+constexpr int kGevD = 26; // doubles per constraint in LDS: vp(3) vn(3) sigma dp(9) sigma dn(9) | tin, row | flags, tinStop (pair constraints: the second point's tin)
 
 __device__ __forceinline__ D3 dnormalizedOrSame(D3 a) { // Eigen normalized(): unchanged when the norm is zero
   const double n2 = ddot(a, a);
   return n2 > 0.0 ? (1.0 / sqrt(n2)) * a : a;
 }
 
-__device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd* js, int joint, size_t c) {
+__device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd* js, int joint, int joint2, size_t c) {
   JointEvalD o;
   o.vp = o.vn = D3{0.0, 0.0, 0.0};
   for (int i = 0; i < 9; ++i) {
@@ -247,6 +247,7 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
   o.nrows = jointBlockFuncDim(k.type);
   o.hasPoint = k.type != MMX_JC_FIXED_AXIS_DIFF && k.type != MMX_JC_FIXED_AXIS_COS && k.type != MMX_JC_FIXED_AXIS_ANGLE;
   o.hasDir = k.type != MMX_JC_PLANE && k.type != MMX_JC_HALF_PLANE && k.type != MMX_JC_PROJECTION && k.type != MMX_JC_DISTANCE;
+  o.pairPoint = k.type == MMX_JC_JOINT_TO_JOINT_DISTANCE;
   bool skip = false; // a projection behind the near plane: no error, rows zero
   const ldsd* w = js + kDs * joint;
   const D3 t{w[0], w[1], w[2]};
@@ -259,11 +260,14 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
     m[3] += f * a.y * b.x, m[4] += f * a.y * b.y, m[5] += f * a.y * b.z;
     m[6] += f * a.z * b.x, m[7] += f * a.z * b.y, m[8] += f * a.z * b.z;
   };
-  const D3 gl = vec(k.global);
+  const D3 gl = o.pairPoint ? D3{0.0, 0.0, 0.0} : vec(k.global); // (the pair type has no world-space payload)
   if (o.hasPoint) {
     o.vp = t + dqrot(q, sc * vec(k.localPoint)); // state.transform * point
   }
-  if (o.hasDir) {
+  if (o.pairPoint) {
+    const ldsd* w2 = js + kDs * joint2;
+    o.vn = D3{w2[0], w2[1], w2[2]} + dqrot(DQ{w2[3], w2[4], w2[5], w2[6]}, w2[7] * vec(k.localDir)); // the second joint's transform * its point
+  } else if (o.hasDir) {
     o.vn = dqrot(q, dnormalizedOrSame(vec(k.localDir))); // state.rotation() * dir, normalised by the data ctor
   }
   switch (k.type) {
@@ -352,6 +356,17 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
       }
       break;
     }
+    case MMX_JC_JOINT_TO_JOINT_DISTANCE: { // f = |x_a - x_b| - d ; df/dx_a = n^T = -df/dx_b, n = (x_a - x_b) / |x_a - x_b|
+      // (two points of ONE joint: s R (o_a - o_b), exactly zero for equal offsets -- see evalJointConstraint)
+      const D3 diff = joint2 == joint ? dqrot(q, sc * (vec(k.localPoint) - vec(k.localDir))) : o.vp - o.vn;
+      const double nrm = sqrt(ddot(diff, diff));
+      o.f[0] = nrm - double(k.planeD[c]);
+      if (nrm > 0.0) {
+        setRow(o.dp, diff, 1.0 / nrm);
+        setRow(o.dn, diff, -1.0 / nrm);
+      }
+      break;
+    }
     default: { // MMX_JC_NORMAL, normal_error_function.cpp:14-31
       const D3 dist = o.vp - gl;
       o.f[0] = ddot(o.vn, dist);
@@ -407,7 +422,7 @@ __device__ double jointBlocksErrorF64(const ProblemDev& pb, const F64Lds& s, int
   double e = 0.0;
   for (int g = tid; g < pb.G; g += 256) {
     const JointBlockDev k = jointBlockOf(pb, b, pb.genBlock[g]);
-    e += evalJointConstraintF64(k, s.js, pb.genJoint[g], size_t(b) * size_t(k.count) + size_t(g - k.first)).werr;
+    e += evalJointConstraintF64(k, s.js, pb.genJoint[g], jointBlockSecondJoint(pb, k, g), size_t(b) * size_t(k.count) + size_t(g - k.first)).werr;
   }
   for (int q = tid; q < pb.NE; q += 256) { // LimitType::Ellipsoid entries of the limit block
     e += evalEllipsoidF64(pb.ellipsoids[q], s.js, pb.wLimit).werr;
@@ -1129,7 +1144,7 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
     for (int g = tid; g < G; g += 256) { // the further joint error functions: residual rows, evaluation record for the Jacobian
       const JointBlockDev k = jointBlockOf(pb, b, pb.genBlock[g]);
       const int i = g - k.first;
-      const JointEvalD o = evalJointConstraintF64(k, s.js, pb.genJoint[g], size_t(b) * size_t(k.count) + size_t(i));
+      const JointEvalD o = evalJointConstraintF64(k, s.js, pb.genJoint[g], jointBlockSecondJoint(pb, k, g), size_t(b) * size_t(k.count) + size_t(i));
       const int row = k.rowStart + o.nrows * i;
       e += o.werr;
       for (int q = 0; q < o.nrows; ++q) {
@@ -1143,7 +1158,8 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
         w[15 + q] = sg * o.dn[q];
       }
       ldsi* wi = reinterpret_cast<ldsi*>(w + 24);
-      wi[0] = pb.genTin[g], wi[1] = row, wi[2] = o.nrows | (o.hasPoint ? 16 : 0) | (o.hasDir ? 32 : 0), wi[3] = -1;
+      wi[0] = pb.genTin[g], wi[1] = row, wi[2] = o.nrows | (o.hasPoint ? 16 : 0) | (o.hasDir ? 32 : 0) | (o.pairPoint ? 64 : 0);
+      wi[3] = jointBlockSecondTin(pb, k, g); // (-1 = no stop position for every other type)
     }
     for (int q = tid; q < pb.NE; q += 256) { // ellipsoid limits: a point constraint whose walk stops at ellipsoidParent
       const EllipsoidDev ct = pb.ellipsoids[q];
@@ -1225,15 +1241,16 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
           const int p = solveList[c];
           const ldsd* w = s.gev + kGevD * g;
           const ldsi* wi = reinterpret_cast<const ldsi*>(w + 24);
-          const int tin = wi[0], row = wi[1], nrows = wi[2] & 15, tinStop = wi[3];
+          const bool pair = (wi[2] & 64) != 0; // two points, two chains: wi[3] is the second point's DFS position
+          const int tin = wi[0], row = wi[1], nrows = wi[2] & 15, tinStop = pair ? -1 : wi[3], tin2 = wi[3];
           const bool hasPoint = (wi[2] & 16) != 0, hasDir = (wi[2] & 32) != 0;
           const D3 vp{w[0], w[1], w[2]}, vn{w[3], w[4], w[5]};
           double acc[3] = {0.0, 0.0, 0.0};
           const int e1 = pb.colStart[p + 1];
           for (int k = pb.colStart[p]; k < e1; ++k) {
             const ColumnSourceDev cs = pb.colSources[k];
-            if (!(cs.tin <= tin && tin < cs.tout)) {
-              continue; // the source's joint is not an ancestor of the constraint's joint
+            if (!(cs.tin <= tin && tin < cs.tout) && !(pair && cs.tin <= tin2 && tin2 < cs.tout)) {
+              continue; // the source's joint is not an ancestor of the constraint's joint (of either joint of a pair)
             }
             if (tinStop >= 0 && cs.tin <= tinStop && tinStop < cs.tout) {
               continue; // ellipsoid limit: the walk stopped before this joint
@@ -1246,8 +1263,8 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
                 gp = D3{0.0, 0.0, 0.0};
               }
             }
-            if (hasDir) {
-              gn = sourceDerivativeF64(cs, s.js, vn, tin, false, ap);
+            if (hasDir) { // (a pair's second vector: a POINT below tin2, so the point rule on its own chain)
+              gn = sourceDerivativeF64(cs, s.js, vn, pair ? tin2 : tin, pair, ap);
               if (!ap) {
                 gn = D3{0.0, 0.0, 0.0};
               }
@@ -1298,15 +1315,16 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
       const int p = solveList[c];
       const ldsd* w = s.gev + kGevD * g;
       const ldsi* wi = reinterpret_cast<const ldsi*>(w + 24);
-      const int tin = wi[0], row = wi[1], nrows = wi[2] & 15, tinStop = wi[3];
+      const bool pair = (wi[2] & 64) != 0; // two points, two chains: wi[3] is the second point's DFS position
+      const int tin = wi[0], row = wi[1], nrows = wi[2] & 15, tinStop = pair ? -1 : wi[3], tin2 = wi[3];
       const bool hasPoint = (wi[2] & 16) != 0, hasDir = (wi[2] & 32) != 0;
       const D3 vp{w[0], w[1], w[2]}, vn{w[3], w[4], w[5]};
       double acc[3] = {0.0, 0.0, 0.0};
       const int e1 = pb.colStart[p + 1];
       for (int k = pb.colStart[p]; k < e1; ++k) {
         const ColumnSourceDev cs = pb.colSources[k];
-        if (!(cs.tin <= tin && tin < cs.tout)) {
-          continue; // the source's joint is not an ancestor of the constraint's joint
+        if (!(cs.tin <= tin && tin < cs.tout) && !(pair && cs.tin <= tin2 && tin2 < cs.tout)) {
+          continue; // the source's joint is not an ancestor of the constraint's joint (of either joint of a pair)
         }
         if (tinStop >= 0 && cs.tin <= tinStop && tinStop < cs.tout) {
           continue; // ellipsoid limit: the walk stopped before this joint
@@ -1319,8 +1337,8 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
             gp = D3{0.0, 0.0, 0.0};
           }
         }
-        if (hasDir) {
-          gn = sourceDerivativeF64(cs, s.js, vn, tin, false, ap);
+        if (hasDir) { // (a pair's second vector: a POINT below tin2, so the point rule on its own chain)
+          gn = sourceDerivativeF64(cs, s.js, vn, pair ? tin2 : tin, pair, ap);
           if (!ap) {
             gn = D3{0.0, 0.0, 0.0};
           }

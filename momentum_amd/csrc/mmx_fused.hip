@@ -62,7 +62,7 @@ struct FusedLds {
   double* red; // [8]
   int* flags; // [4]: stop | not positive definite (this iteration) | status | unused
   // ---- rows of the further joint error functions and ellipsoid limits (kGen instantiations): dense in LDS
-  float* gEv; // [GT][kGenEv] per constraint: vp(3) vn(3) sigma*dp(9) sigma*dn(9) tin row flags tinStop
+  float* gEv; // [GT][kGenEv] per constraint: vp(3) vn(3) sigma*dp(9) sigma*dn(9) tin row flags tinStop (pair constraints: the second point's tin)
   float* gRes; // [rowsGp] residual rows
   float* gW; // [rowsGp] r - J d of the refinement
   float* gJ; // [rowsGp][gst] their Jacobian rows over the solve columns (pad rows / columns zero)
@@ -830,7 +830,7 @@ __device__ __forceinline__ double generalRowsError(const ProblemDev& pb, const f
   double e = 0.0;
   for (int g = tid; g < pb.G; g += 256) {
     const JointBlockDev k = jointBlockOf(pb, b, pb.genBlock[g]);
-    e += double(evalJointConstraint(k, js, pb.genJoint[g], size_t(b) * size_t(k.count) + size_t(g - k.first)).werr);
+    e += double(evalJointConstraint(k, js, pb.genJoint[g], jointBlockSecondJoint(pb, k, g), size_t(b) * size_t(k.count) + size_t(g - k.first)).werr);
   }
   if (pb.wLimit > 0.f) {
     const float tWeightE = 1e+1f * pb.wLimit;
@@ -850,7 +850,7 @@ __device__ __forceinline__ double generalRowsEvaluate(const ProblemDev& pb, cons
   for (int g = tid; g < pb.G; g += 256) {
     const JointBlockDev k = jointBlockOf(pb, b, pb.genBlock[g]);
     const int i = g - k.first;
-    const JointEval o = evalJointConstraint(k, js, pb.genJoint[g], size_t(b) * size_t(k.count) + size_t(i));
+    const JointEval o = evalJointConstraint(k, js, pb.genJoint[g], jointBlockSecondJoint(pb, k, g), size_t(b) * size_t(k.count) + size_t(i));
     const int row = k.rowStart + o.nrows * i - 3 * U;
     e += double(o.werr);
     for (int q = 0; q < o.nrows; ++q) {
@@ -867,8 +867,8 @@ __device__ __forceinline__ double generalRowsEvaluate(const ProblemDev& pb, cons
     }
     evi[kGenEv * g + 24] = pb.genTin[g];
     evi[kGenEv * g + 25] = row;
-    evi[kGenEv * g + 26] = o.nrows | (o.hasPoint ? 16 : 0) | (o.hasDir ? 32 : 0);
-    evi[kGenEv * g + 27] = -1;
+    evi[kGenEv * g + 26] = jointEvalFlags(o);
+    evi[kGenEv * g + 27] = jointBlockSecondTin(pb, k, g); // (-1 = no stop position for every other type)
   }
   const float tWeightE = 1e+1f * pb.wLimit;
   for (int q = tid; q < pb.NE; q += 256) { // LimitType::Ellipsoid (limit_error_function.cpp:702-790), see jointBlocksKernel
@@ -942,11 +942,29 @@ __device__ __forceinline__ void generalRowsGather(const float* js, const float* 
         acc[q] += jc * sl.weight;
       }
     };
-    addSlot(c);
+    // a pair constraint (flag 64): two points on two chains, word 27 is the second point's DFS position (no stop position).
+    // One row, sigma n^T d(x_a - x_b): the second point's share is folded into the derivative (its df/dv is -dp).
+    auto addSlotPair = [&](int e) {
+      const GenSlot sl = slot(e);
+      const bool anc = sl.tin <= tin && tin < sl.tout, anc2 = sl.tin <= tinStop && tinStop < sl.tout;
+      if (!anc && !anc2) {
+        return; // the slot's joint is above neither joint of the pair
+      }
+      const F3 gd = pairSourceDerivative(js, sl.joint, sl.dof, anc, anc2, vp, vn, [&]() { return transAxisCol(js, sl.parent, sl.dof); });
+      acc[0] += (w[6] * gd.x + w[7] * gd.y + w[8] * gd.z) * sl.weight;
+    };
     int e0, e1;
     extras(c, e0, e1);
-    for (int e = e0; e < e1; ++e) {
-      addSlot(e);
+    if ((fl & 64) != 0) { // (uniform per record; the other types walk exactly as before)
+      addSlotPair(c);
+      for (int e = e0; e < e1; ++e) {
+        addSlotPair(e);
+      }
+    } else {
+      addSlot(c);
+      for (int e = e0; e < e1; ++e) {
+        addSlot(e);
+      }
     }
     gJ[row * gst + c] = acc[0];
     if ((fl & 15) >= 2) {

@@ -747,7 +747,7 @@ __global__ void __launch_bounds__(256) jointBlocksKernel(
   for (int g = tid; g < G; g += 256) {
     const JointBlockDev k = jointBlockOf(pb, b, pb.genBlock[g]);
     const int i = g - k.first;
-    const JointEval o = evalJointConstraint(k, js, pb.genJoint[g], size_t(b) * size_t(k.count) + size_t(i));
+    const JointEval o = evalJointConstraint(k, js, pb.genJoint[g], jointBlockSecondJoint(pb, k, g), size_t(b) * size_t(k.count) + size_t(i));
     const int row = k.rowStart + o.nrows * i;
     e += double(o.werr);
     if (res != nullptr) {
@@ -768,8 +768,8 @@ __global__ void __launch_bounds__(256) jointBlocksKernel(
       }
       evi[kEvWords * g + 24] = pb.genTin[g];
       evi[kEvWords * g + 25] = row;
-      evi[kEvWords * g + 26] = o.nrows | (o.hasPoint ? 16 : 0) | (o.hasDir ? 32 : 0);
-      evi[kEvWords * g + 27] = -1;
+      evi[kEvWords * g + 26] = jointEvalFlags(o);
+      evi[kEvWords * g + 27] = jointBlockSecondTin(pb, k, g); // (-1 = no stop position for every other type)
     }
   }
   // LimitType::Ellipsoid entries: a point constraint whose target (the projection onto the ellipsoid)
@@ -823,7 +823,8 @@ __global__ void __launch_bounds__(256) jointBlocksKernel(
     const int p = item / GT, g = item - p * GT; // constraints fastest: neighbouring threads write neighbouring rows
     const float* w = ev + kEvWords * g;
     const int tin = evi[kEvWords * g + 24], row = evi[kEvWords * g + 25], fl = evi[kEvWords * g + 26];
-    const int tinStop = evi[kEvWords * g + 27];
+    const bool pair = (fl & 64) != 0; // two points, two chains: word 27 is the second point's DFS position
+    const int tinStop = pair ? -1 : evi[kEvWords * g + 27], tin2 = evi[kEvWords * g + 27];
     const int nrows = fl & 15;
     const bool hasPoint = (fl & 16) != 0, hasDir = (fl & 32) != 0;
     const F3 vp{w[0], w[1], w[2]}, vn{w[3], w[4], w[5]};
@@ -831,15 +832,26 @@ __global__ void __launch_bounds__(256) jointBlocksKernel(
     const int e1 = pb.colStart[p + 1];
     for (int ei = pb.colStart[p]; ei < e1; ++ei) {
       const ColumnSourceDev s = pb.colSources[ei];
-      if (!((s.tin <= tin) && (tin < s.tout))) {
-        continue; // the source's joint is not an ancestor of the constraint's joint
+      const bool anc = (s.tin <= tin) && (tin < s.tout);
+      const bool anc2 = pair && (s.tin <= tin2) && (tin2 < s.tout);
+      if (!anc && !anc2) {
+        continue; // the source's joint is not an ancestor of the constraint's joint (of either joint of a pair)
       }
       if (tinStop >= 0 && s.tin <= tinStop && tinStop < s.tout) {
         continue; // ellipsoid limit: the walk stopped before this joint
       }
       const float* a = js + kJs * s.joint;
       F3 gp{0.f, 0.f, 0.f}, gn{0.f, 0.f, 0.f};
-      if (s.dof >= 3 && s.dof < 6) { // rotation: axis x (v - t_a) for points, axis x v for directions (:265-278)
+      if (pair) { // d(x_a - x_b): the second point's share is folded into gp (its df/dv is -dp), gn stays zero
+        gp = pairSourceDerivative(js, s.joint, s.dof, anc, anc2, vp, vn, [&]() {
+          if (s.parent < 0) {
+            return F3{s.dof == 0 ? 1.f : 0.f, s.dof == 1 ? 1.f : 0.f, s.dof == 2 ? 1.f : 0.f};
+          }
+          const float* pp = js + kJs * s.parent;
+          const F3 c = qmatCol(Q4{pp[3], pp[4], pp[5], pp[6]}, s.dof);
+          return F3{c.x * pp[7], c.y * pp[7], c.z * pp[7]};
+        });
+      } else if (s.dof >= 3 && s.dof < 6) { // rotation: axis x (v - t_a) for points, axis x v for directions (:265-278)
         const float* ax = a + 8 + 3 * (s.dof - 3);
         const F3 axis{ax[0], ax[1], ax[2]};
         if (hasPoint) {
@@ -3238,7 +3250,7 @@ __global__ void __launch_bounds__(256) stepUpdateKernel(
     }
     for (int g = tid; g < pb.G; g += 256) {
       const JointBlockDev k = jointBlockOf(pb, b, pb.genBlock[g]);
-      e += double(evalJointConstraint(k, sl.js, pb.genJoint[g], size_t(b) * size_t(k.count) + size_t(g - k.first)).werr);
+      e += double(evalJointConstraint(k, sl.js, pb.genJoint[g], jointBlockSecondJoint(pb, k, g), size_t(b) * size_t(k.count) + size_t(g - k.first)).werr);
     }
     if (pb.wLimit > 0.f) {
       for (int q = tid; q < pb.NE; q += 256) {

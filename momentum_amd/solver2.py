@@ -5,7 +5,8 @@ Same class and argument names as the reference's binding (pymomentum/solver2/sol
 solver2_error_functions.cpp:340-442 PositionErrorFunction, :1094-1200 OrientationErrorFunction,
 :263-283 ModelParametersErrorFunction; solver2_distance_error_functions.cpp:93-201 NormalErrorFunction,
 :430-530 PlaneErrorFunction; solver2_aim_axis_error_functions.cpp:57-282 Aim* / FixedAxis*; Projection- and
-DistanceErrorFunction after the reference's classes of those names, without citations: include/mmx.h), so a
+Distance- and JointToJointDistanceErrorFunction after the reference's classes of those names, without citations:
+include/mmx.h), so a
 call site written against pymomentum.solver2 reads the same here.  Differences, all additive:
 
 * everything is BATCHED: `solve` takes model parameters [P] or [B, P]; constraint payloads
@@ -327,6 +328,46 @@ class DistanceErrorFunction(_BlockErrorFunction):
         self._add_many(parent, weight, name, origin=origin, target=target, offset=np.zeros_like(origin) if offset is None else offset)
 
 
+class JointToJointDistanceErrorFunction(_BlockErrorFunction):
+    """JointToJointDistanceErrorFunctionT: the distance between the point `offset1` of joint `joint1` and the point
+    `offset2` of joint `joint2` pulled to `target_distance` (include/mmx.h, MMX_JC_JOINT_TO_JOINT_DISTANCE).  The
+    joints are shared by the batch; the two may coincide or lie on one chain.  L2 loss only."""
+
+    TYPE = _abi.MMX_JC_JOINT_TO_JOINT_DISTANCE
+    FIELDS = (("offset1", 3), ("offset2", 3), ("target_distance", 0))
+    MAP = {"local_point": "offset1", "local_dir": "offset2", "plane_d": "target_distance"}
+
+    def __init__(self, character, weight: float = 1.0):
+        super().__init__(character, 2.0, 1.0, weight)
+        self._joint2: List[int] = []  # the second joint of constraint k (the first is its `parent`)
+
+    def clear_constraints(self) -> None:
+        super().clear_constraints()
+        self._joint2.clear()
+
+    def block(self, B: int) -> JointBlock:
+        parents, weights, data = self._stack(B)
+        kw = {bf: data[cf] for bf, cf in self.MAP.items()}
+        return JointBlock(self.TYPE, parents, weights, None, function_weight=self.weight, loss=(self.alpha, self.c),
+                          parent_b=np.array(self._joint2, np.int32), **kw)  # fmt: skip
+
+    def add_constraint(self, joint1, offset1, joint2, offset2, target_distance, weight: float = 1.0, name: str = "") -> None:
+        joint2 = int(joint2)
+        if joint2 < 0 or joint2 >= self.character.skeleton.size:
+            raise RuntimeError(f"Invalid joint index {joint2}")
+        self._add(joint1, weight, name, offset1=offset1, offset2=offset2, target_distance=target_distance)
+        self._joint2.append(joint2)
+
+    def add_constraints(self, joint1, offset1, joint2, offset2, target_distance, weight=None, name=None) -> None:
+        joint2 = np.asarray(joint2, dtype=np.int64).reshape(-1)
+        if joint2.shape[0] != np.asarray(joint1).reshape(-1).shape[0]:
+            raise ValueError("joint1 and joint2 differ in length")
+        if np.any(joint2 < 0) or np.any(joint2 >= self.character.skeleton.size):
+            raise RuntimeError("Invalid joint index in joint2")
+        self._add_many(joint1, weight, name, offset1=offset1, offset2=offset2, target_distance=target_distance)
+        self._joint2.extend(int(j) for j in joint2)
+
+
 class LimitErrorFunction(SkeletonErrorFunction):
     """LimitErrorFunctionT on the character's parameter limits (limit_error_function.h:45-110);
     limit types MinMax / MinMaxJoint / Linear / LinearJoint / HalfPlane (ParameterLimit) and Ellipsoid
@@ -426,7 +467,7 @@ class SkeletonSolverFunction(SolverFunction):
         pp, po, pt, pw, ploss = self._merged(PositionErrorFunction, B, 3)
         op, oo, ot, ow, oloss = self._merged(OrientationErrorFunction, B, 4)
         blocks = [e.block(B) for e in self._efs if isinstance(e, _BlockErrorFunction) and e._constraints]
-        key = (B, pp.tobytes(), op.tobytes(), tuple((b.type, b.parent.tobytes()) for b in blocks))
+        key = (B, pp.tobytes(), op.tobytes(), tuple((b.type, b.parent_array().tobytes()) for b in blocks))
         if self._cache is None or self._cache[0] != key:
             if self._cache is not None:
                 self._cache[1].close()
