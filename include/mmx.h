@@ -576,11 +576,25 @@ typedef struct mmx_tuning {
                             then holds on every element whose double run amplifies a 1e-12 perturbation by less than 1e5; 1e-7
                             costs 15 % less and holds it where the amplification stays below 1e2) */
   int32_t mixed_max_cg; /* ... and after at most this many operator applications (0 = the default, 12) */
-  int32_t reserved[4]; /* must be zero */
+  int32_t joint_pruning; /* (out of the reserved words, same size; no ABI bump: a library that predates it answers -1 with
+                            MMX_ERR_INVALID_ARGUMENT) 0 = the default, on: the one-launch solve, its mixed-precision
+                            instantiation, the wave route and the wide route's tree kernels run over the LIVE joints only --
+                            the ancestors-or-self of every joint the problem references (constraint parents, both joints of
+                            the further blocks and of ellipsoid limits, the joints of joint-parameter limits), renumbered by
+                            monotone maps.  A joint outside that set has no constraint below it: its columns are structurally
+                            zero and nothing the solve returns reads its state, so results are BIT-IDENTICAL either way
+                            (tests/test_gpu_live_joints.py).  -1 = off (a measurement switch, like max_refinement_steps = -1).
+                            Nothing is pruned with per-instance rigs or constraint parents, when every joint is live or when
+                            none is referenced.  Routes, instantiations and LDS budgets are chosen from the full joint count
+                            in both settings. */
+  int32_t reserved[3]; /* must be zero */
 } mmx_tuning;
 int32_t mmx_problem_set_tuning(mmx_problem* problem, const mmx_tuning* tuning);
 /* MMX_ROUTE_* the last mmx_solve / mmx_solve_with_history on this handle took (MMX_ROUTE_AUTO before the first). */
 int32_t mmx_problem_last_route(const mmx_problem* problem);
+/* The joint count the solve kernels named under mmx_tuning::joint_pruning run over with the problem's current tables and
+ * tuning: the live joints, or mmx_rig_num_joints when nothing is pruned.  (Additive, host-side query.) */
+int32_t mmx_problem_num_solve_joints(const mmx_problem* problem);
 
 /* M = 3*Kp + 9*Ko + rows of the further blocks and parameter-space blocks
  * (JointErrorFunctionT::getJacobianSize, joint_error_function-inl.h:300-302). */
@@ -900,6 +914,13 @@ int32_t mmx_host_tables(
  */
 int32_t mmx_host_elimination_order(const mmx_rig_desc* desc, const uint8_t* enabled, int32_t* order, int32_t* num_enabled);
 int32_t mmx_host_tile_structure(int32_t n, const uint8_t* related, uint32_t* row_mask, uint32_t* col_mask, int64_t* products);
+/*
+ *   mmx_host_live_joints: the live-joint bookkeeping of mmx_tuning::joint_pruning for a list of n referenced joints --
+ *     live[J] (1 = the joint or one of its descendants is referenced), compact_of[J] (its index among the live joints,
+ *     ascending in joint index, -1 for a dead joint), *num_live.  With no referenced joint nothing is pruned: every joint
+ *     is live and compact_of is the identity.  Outputs may be null.  Host-only bookkeeping (additive).
+ */
+int32_t mmx_host_live_joints(const mmx_rig_desc* desc, int32_t n, const int32_t* joints, uint8_t* live, int32_t* compact_of, int32_t* num_live);
 int32_t mmx_problem_tile_structure(mmx_problem* problem, uint32_t* row_mask, uint32_t* col_mask, int32_t* num_blocks, int32_t* num_tiles, int64_t* products);
 /*
  *   mmx_host_tile_level_schedule: the order the resident factor kernel takes the block columns of that structure in --

@@ -355,7 +355,7 @@ WAVE_MAX_UNITS = 192
 class Tuning(C.Structure):
     """mmx_tuning: which kernels mmx_solve runs (include/mmx.h)."""
 
-    _fields_ = [("route", C.c_int32), ("max_refinement_steps", C.c_int32), ("mixed_tolerance", C.c_float), ("mixed_max_cg", C.c_int32), ("reserved", C.c_int32 * 4)]
+    _fields_ = [("route", C.c_int32), ("max_refinement_steps", C.c_int32), ("mixed_tolerance", C.c_float), ("mixed_max_cg", C.c_int32), ("joint_pruning", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 def as_ptr(a: np.ndarray, ctype):

@@ -26,11 +26,11 @@ SYMBOLS = [
     "mmx_gn_options_default", "mmx_abi_version", "mmx_last_error", "mmx_device_count",
     "mmx_rig_create", "mmx_rig_destroy", "mmx_rig_num_joints", "mmx_rig_num_params",
     "mmx_problem_create", "mmx_problem_destroy", "mmx_problem_num_rows", "mmx_problem_batch",
-    "mmx_problem_set_tuning", "mmx_problem_last_route",
+    "mmx_problem_set_tuning", "mmx_problem_last_route", "mmx_problem_num_solve_joints",
     "mmx_problem_set_enabled", "mmx_problem_set_constraints", "mmx_problem_set_constraints_sized", "mmx_problem_set_instance_rig", "mmx_problem_set_instance_parents", "mmx_eval_jacobian", "mmx_eval_jacobian_timed", "mmx_debug_store_pattern",
     "mmx_eval_skeleton_state", "mmx_eval_normal_equations", "mmx_solve", "mmx_solve_with_history", "mmx_solve_with_step_history", "mmx_problem_solve_diagnostics", "mmx_solve_f64", "mmx_solve_f64_host", "mmx_solve_host",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
-    "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure",
+    "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
     "mmx_comm_all_reduce_norms", "mmx_comm_all_reduce_norms_host", "mmx_residual_norms", "mmx_comm_destroy",
 ]  # fmt: skip
@@ -73,6 +73,7 @@ def lib() -> C.CDLL:
     L.mmx_problem_set_enabled.argtypes = [vp, _abi.c_uint8_p]
     L.mmx_problem_set_tuning.argtypes = [vp, C.POINTER(_abi.Tuning)]
     L.mmx_problem_last_route.argtypes = [vp]
+    L.mmx_problem_num_solve_joints.argtypes = [vp]
     L.mmx_problem_set_constraints.argtypes = [vp, C.POINTER(ConstraintData), vp]
     L.mmx_problem_set_constraints_sized.argtypes = [vp, C.POINTER(ConstraintData), C.c_size_t, vp]
     L.mmx_problem_set_instance_rig.argtypes = [vp, vp, vp, i32, vp]
@@ -112,6 +113,7 @@ def lib() -> C.CDLL:
     L.mmx_host_tile_structure.argtypes = [i32, _abi.c_uint8_p, u32p, u32p, i64p]
     L.mmx_host_tile_level_schedule.argtypes = [i32, _abi.c_uint8_p, C.POINTER(C.c_int32)]
     L.mmx_problem_tile_structure.argtypes = [vp, u32p, u32p, _abi.c_int32_p, _abi.c_int32_p, i64p]
+    L.mmx_host_live_joints.argtypes = [C.POINTER(RigDesc), i32, _abi.c_int32_p, _abi.c_uint8_p, _abi.c_int32_p, _abi.c_int32_p]
     _lib = L
     return L
 
@@ -148,6 +150,19 @@ def host_tables(rig: Rig, enabled=None) -> dict:
     _check(lib().mmx_host_elimination_order(C.byref(d), eptr, as_ptr(order, C.c_int32), C.byref(n)))
     return dict(level=level, tin=tin, tout=tout, active_joint_params=active, enabled_list=elist[: n.value].copy(),
                 elimination_order=order[: n.value].copy())  # fmt: skip
+
+
+def host_live_joints(rig: Rig, joints) -> dict:
+    """The live-joint bookkeeping of mmx_tuning::joint_pruning (mmx_host_live_joints) for a list of referenced joints:
+    dict(live [J] uint8, compact_of [J] int32 (-1 = dead), num_live)."""
+    J = rig.num_joints
+    jl = np.ascontiguousarray(joints, dtype=np.int32).reshape(-1)
+    live, compact = np.zeros(J, np.uint8), np.zeros(J, np.int32)
+    n = C.c_int32(0)
+    d = rig.desc()
+    jptr = as_ptr(jl, C.c_int32) if jl.size else _abi.c_int32_p()
+    _check(lib().mmx_host_live_joints(C.byref(d), C.c_int32(jl.size), jptr, as_ptr(live, C.c_uint8), as_ptr(compact, C.c_int32), C.byref(n)))
+    return dict(live=live, compact_of=compact, num_live=int(n.value))
 
 
 def host_tile_structure(related: np.ndarray):
@@ -298,6 +313,7 @@ class Problem:
         t.route = _abi.ROUTES[route]
         t.max_refinement_steps = int(max_refinement_steps)  # 0 default (up to three), -1 none, 1..3
         t.mixed_tolerance, t.mixed_max_cg = getattr(self, "_mixed", (0.0, 0))  # MMX_PRECISION_MIXED: 0 = defaults (3e-9, 12)
+        t.joint_pruning = 0 if getattr(self, "_joint_pruning", True) else -1
         self._route_args = (route, int(max_refinement_steps))
         _check(lib().mmx_problem_set_tuning(self._h, C.byref(t)))
 
@@ -305,6 +321,16 @@ class Problem:
         """mmx_tuning::mixed_tolerance / mixed_max_cg (MMX_PRECISION_MIXED); the route setting is kept."""
         self._mixed = (float(tolerance), int(max_cg))
         self._set_tuning(*getattr(self, "_route_args", ("auto", 0)))
+
+    def set_joint_pruning(self, on: bool = True) -> None:
+        """mmx_tuning::joint_pruning: the solve kernels run over the live joints only (the default) or over every joint
+        (a measurement switch: results are bit-identical); the route and mixed settings are kept."""
+        self._joint_pruning = bool(on)
+        self._set_tuning(*getattr(self, "_route_args", ("auto", 0)))
+
+    def num_solve_joints(self) -> int:
+        """Joints the solve kernels run over (mmx_problem_num_solve_joints): the live ones, or all when nothing is pruned."""
+        return int(lib().mmx_problem_num_solve_joints(self._h))
 
     def last_route(self) -> str:
         r = int(lib().mmx_problem_last_route(self._h))

@@ -236,6 +236,15 @@ struct mmx_problem {
   bool autoAbort = false; // ... its single-precision pass may leave a marked element after the first factorisation
   mmx_tuning tuning{}; // mmx_problem_set_tuning
   int32_t lastRoute = MMX_ROUTE_AUTO;
+  // The live-joint view (solveView below): the rig and the joint-indexed tables over the joints the solve can depend on,
+  // renumbered.  Built by uploadProblemTables when it prunes something; what the one-launch, mixed, wave and tree kernels get.
+  mmx::LiveJoints liveJoints;
+  bool viewBuilt = false;
+  mmx::RigDev vRig{};
+  int32_t vNnz = 0;
+  DevBuf vParent, vPreRot, vOffset, vPtOuter, vPtInner, vPtValue, vPtOffsets, vLevelOrder, vLevelStart, vPtEll, vJumpParent, vPtRowRec;
+  DevBuf vUnitJoint, vUnitTin, vJointTin, vGenJoint, vGenTin, vEllipsoids, vLimits;
+  DevBuf vSubSize, vDfsJoint, vLoadedPos, vPosUnitStart, vSrcs;
 };
 
 namespace {
@@ -273,6 +282,282 @@ std::vector<int32_t> limitParameters(const mmx_rig* rig, const mmx_parameter_lim
       break;
   }
   return out;
+}
+
+// Tables derived from a rig's host arrays: the two-slot ELL copy of the parameter transform (one 16-byte record per
+// joint-parameter row), the packed parent / jump-target table, the records of the non-empty transform rows
+// (RigDev::ptRowRec) and the pointer-jumping round count.  mmx_rig_create builds them for the rig, the live-joint view of a
+// problem for its joints.
+struct RigDerived {
+  std::vector<int32_t> ell, jumpParent, rowRec;
+  bool ellOk = true;
+  int32_t jumpRounds = 0;
+};
+RigDerived deriveRigTables(
+    int32_t J, int32_t P, const std::vector<int32_t>& parent, const std::vector<int32_t>& ptOuter, const std::vector<int32_t>& ptInner,
+    const std::vector<float>& ptValue, int32_t numLevels) {
+  RigDerived o;
+  const int32_t R = MMX_PARAMS_PER_JOINT * J;
+  o.ell.assign(size_t(R) * 4, 0);
+  o.jumpParent.assign(size_t(J), 0);
+  for (int32_t row = 0; row < R; ++row) {
+    const int32_t k0 = ptOuter[size_t(row)], k1 = ptOuter[size_t(row) + 1];
+    if (k1 - k0 > 2) {
+      o.ellOk = false;
+      break;
+    }
+    for (int s = 0; s < 2; ++s) {
+      int32_t idx = -1, bits = 0;
+      if (k0 + s < k1) {
+        idx = ptInner[size_t(k0 + s)];
+        std::memcpy(&bits, &ptValue[size_t(k0 + s)], 4);
+      }
+      o.ell[4 * size_t(row) + 2 * s] = idx;
+      o.ell[4 * size_t(row) + 2 * s + 1] = bits;
+    }
+  }
+  for (int32_t j = 0; j < J; ++j) {
+    o.jumpParent[size_t(j)] = ((parent[size_t(j)] + 1) << 16) | (parent[size_t(j)] + 1);
+  }
+  if (R < 65536 && P <= 65535) { // (every field of a record is an unsigned 16-bit number: row, rows to the next record, first column, entries)
+    std::vector<int32_t> rows;
+    for (int32_t row = 0; row < R; ++row) {
+      if (ptOuter[size_t(row) + 1] > ptOuter[size_t(row)]) {
+        rows.push_back(row);
+      }
+    }
+    for (size_t t = 0; t < rows.size(); ++t) {
+      const int32_t row = rows[t], next = t + 1 < rows.size() ? rows[t + 1] : R;
+      const int32_t k0 = ptOuter[size_t(row)], cnt = ptOuter[size_t(row) + 1] - k0;
+      if (cnt > 65535 || next - row > 65535) { // (does not fit: no records at all, the kernels walk the CSR)
+        o.rowRec.clear();
+        break;
+      }
+      int32_t bits = 0;
+      std::memcpy(&bits, &ptValue[size_t(k0)], 4);
+      o.rowRec.insert(o.rowRec.end(), {row | ((next - row) << 16), ptInner[size_t(k0)] | (cnt << 16), bits, k0});
+    }
+  }
+  while ((1 << o.jumpRounds) < numLevels) {
+    ++o.jumpRounds;
+  }
+  return o;
+}
+
+// The joints the problem references (mmx_host_tables.hpp, LiveJoints): constraint parents, the joints of the further blocks
+// and of ellipsoid limits, the joints of joint-parameter limits.
+std::vector<int32_t> referencedJoints(const mmx_problem* pb) {
+  std::vector<int32_t> ref(pb->posParent);
+  ref.insert(ref.end(), pb->oriParent.begin(), pb->oriParent.end());
+  for (const auto& h : pb->blocks) {
+    ref.insert(ref.end(), h->parent.begin(), h->parent.end());
+    ref.insert(ref.end(), h->parentB.begin(), h->parentB.end());
+  }
+  for (const mmx_ellipsoid_limit& e : pb->ellipsoids) {
+    ref.push_back(e.parent);
+    ref.push_back(e.ellipsoid_parent);
+  }
+  for (const mmx_parameter_limit& lm : pb->limits) {
+    if (lm.type == MMX_LIMIT_MINMAX_JOINT || lm.type == MMX_LIMIT_LINEAR_JOINT) {
+      ref.push_back(lm.index0 / MMX_PARAMS_PER_JOINT);
+    }
+    if (lm.type == MMX_LIMIT_LINEAR_JOINT) {
+      ref.push_back(lm.index1 / MMX_PARAMS_PER_JOINT);
+    }
+  }
+  return ref;
+}
+
+// The live-joint view's tables: everything the solve kernels index by joint or by DFS position, REMAPPED from the tables
+// uploadProblemTables has just built (solve list, elimination order, slots, term records and tile structure stay as they are).
+// Off -- the kernels keep the full descriptors -- with per-instance constraint parents (their lists name full joint ids; the
+// per-instance rig arrays are looked at per solve, solveView) and when nothing would be pruned.
+int32_t uploadSolveView(mmx_problem* pb, const std::vector<mmx::ColumnSource>& slots) {
+  const mmx_rig* rig = pb->rig;
+  pb->viewBuilt = false;
+  const std::vector<int32_t> ref = referencedJoints(pb);
+  mmx::LiveJoints& lj = pb->liveJoints;
+  mmx::buildLiveJoints(rig->parent.data(), rig->J, ref.data(), int32_t(ref.size()), lj);
+  if (lj.identity() || pb->instPos || pb->instOri) {
+    return MMX_OK;
+  }
+  const mmx::HostTables& t = pb->tables;
+  const mmx::FusedTables& f = pb->fused;
+  const int32_t J = rig->J, Jc = lj.numLive;
+  const size_t nJ = size_t(J), nJc = size_t(Jc), nU = size_t(std::max(pb->U, 1));
+  // ---- the rig over the live joints
+  std::vector<int32_t> parent(nJc), ptOuter(1, 0), ptInner;
+  std::vector<float> preRot(4 * nJc), offset(3 * nJc), ptValue, ptOffsets;
+  for (int32_t c = 0; c < Jc; ++c) {
+    const int32_t j = lj.fullOf[size_t(c)];
+    parent[size_t(c)] = rig->parent[size_t(j)] < 0 ? rig->parent[size_t(j)] : lj.compactOf[size_t(rig->parent[size_t(j)])];
+    std::copy_n(&rig->preRot[4 * size_t(j)], 4, &preRot[4 * size_t(c)]);
+    std::copy_n(&rig->offset[3 * size_t(j)], 3, &offset[3 * size_t(c)]);
+    for (int32_t d = 0; d < MMX_PARAMS_PER_JOINT; ++d) {
+      const size_t row = size_t(MMX_PARAMS_PER_JOINT) * size_t(j) + size_t(d);
+      ptInner.insert(ptInner.end(), rig->ptInner.begin() + rig->ptOuter[row], rig->ptInner.begin() + rig->ptOuter[row + 1]);
+      ptValue.insert(ptValue.end(), rig->ptValue.begin() + rig->ptOuter[row], rig->ptValue.begin() + rig->ptOuter[row + 1]);
+      ptOuter.push_back(int32_t(ptInner.size()));
+      ptOffsets.push_back(rig->ptOffsets[row]);
+    }
+  }
+  // levels and the DFS interval of every live joint in the compact numbering: a live joint's ancestors are live, so its level
+  // is the full rig's, and the live positions keep their order (rank among the live positions)
+  std::vector<int32_t> levelStart, levelOrder(nJc), posOf(nJ, -1), cTin(nJc), cTout(nJc);
+  {
+    int32_t maxLevel = 0;
+    for (int32_t j : lj.fullOf) {
+      maxLevel = std::max(maxLevel, t.level[size_t(j)]);
+    }
+    levelStart.assign(size_t(maxLevel) + 2, 0);
+    for (int32_t j : lj.fullOf) {
+      levelStart[size_t(t.level[size_t(j)]) + 1]++;
+    }
+    for (int32_t l = 0; l <= maxLevel; ++l) {
+      levelStart[size_t(l) + 1] += levelStart[size_t(l)];
+    }
+    std::vector<int32_t> cursor(levelStart.begin(), levelStart.end() - 1);
+    for (int32_t c = 0; c < Jc; ++c) {
+      levelOrder[size_t(cursor[size_t(t.level[size_t(lj.fullOf[size_t(c)])])]++)] = c;
+    }
+    int32_t next = 0;
+    for (int32_t k = 0; k < J; ++k) { // full DFS positions, ascending
+      if (lj.live[size_t(f.dfsJoint[size_t(k)])]) {
+        posOf[size_t(k)] = next++;
+      }
+    }
+    std::vector<int32_t> liveBefore(nJ + 1, 0); // live positions before full position k
+    for (int32_t k = 0; k < J; ++k) {
+      liveBefore[size_t(k) + 1] = liveBefore[size_t(k)] + (posOf[size_t(k)] >= 0 ? 1 : 0);
+    }
+    for (int32_t c = 0; c < Jc; ++c) {
+      const int32_t j = lj.fullOf[size_t(c)];
+      cTin[size_t(c)] = liveBefore[size_t(t.tin[size_t(j)])];
+      cTout[size_t(c)] = liveBefore[size_t(t.tout[size_t(j)])];
+    }
+  }
+  const int32_t numLevels = int32_t(levelStart.size()) - 1;
+  const RigDerived rd = deriveRigTables(Jc, rig->P, parent, ptOuter, ptInner, ptValue, numLevels);
+  MMX_HIP(upload(pb->vParent, parent));
+  MMX_HIP(upload(pb->vPreRot, preRot));
+  MMX_HIP(upload(pb->vOffset, offset));
+  MMX_HIP(upload(pb->vPtOuter, ptOuter));
+  MMX_HIP(upload(pb->vPtInner, ptInner));
+  MMX_HIP(upload(pb->vPtValue, ptValue));
+  MMX_HIP(upload(pb->vPtOffsets, ptOffsets));
+  MMX_HIP(upload(pb->vLevelOrder, levelOrder));
+  MMX_HIP(upload(pb->vLevelStart, levelStart));
+  if (rd.ellOk) {
+    MMX_HIP(upload(pb->vPtEll, rd.ell));
+  }
+  MMX_HIP(upload(pb->vJumpParent, rd.jumpParent));
+  if (!rd.rowRec.empty()) {
+    MMX_HIP(upload(pb->vPtRowRec, rd.rowRec));
+  }
+  mmx::RigDev& v = pb->vRig;
+  v = rig->dev; // P, ptOffsetsNonZero (a dead row's offset moves nothing the solve reads), layoutJ = the full rig's count
+  v.J = Jc;
+  v.R = MMX_PARAMS_PER_JOINT * Jc;
+  v.numLevels = numLevels;
+  v.parent = pb->vParent.as<int32_t>();
+  v.preRot = pb->vPreRot.as<float>();
+  v.offset = pb->vOffset.as<float>();
+  v.ptOuter = pb->vPtOuter.as<int32_t>();
+  v.ptInner = pb->vPtInner.as<int32_t>();
+  v.ptValue = pb->vPtValue.as<float>();
+  v.ptOffsets = pb->vPtOffsets.as<float>();
+  v.levelOrder = pb->vLevelOrder.as<int32_t>();
+  v.levelStart = pb->vLevelStart.as<int32_t>();
+  v.ptEll = rd.ellOk ? pb->vPtEll.as<int4>() : nullptr;
+  v.ptRowRec = rd.rowRec.empty() ? nullptr : pb->vPtRowRec.as<int4>();
+  v.numRowRec = int32_t(rd.rowRec.size() / 4);
+  v.jumpParent = pb->vJumpParent.as<int32_t>();
+  v.jumpRounds = rd.jumpRounds;
+  v.instPreRot = nullptr;
+  v.instOffset = nullptr;
+  pb->vNnz = ptOuter.back();
+  // ---- the problem's joint-indexed tables
+  auto cj = [&](int32_t j) { return j < 0 ? j : lj.compactOf[size_t(j)]; };
+  std::vector<int32_t> unitJoint(nU, 0), unitTin(nU, 0);
+  for (int32_t u = 0; u < pb->U; ++u) {
+    unitJoint[size_t(u)] = cj(f.unitJoint[size_t(u)]);
+    unitTin[size_t(u)] = cTin[size_t(unitJoint[size_t(u)])];
+  }
+  MMX_HIP(upload(pb->vUnitJoint, unitJoint));
+  MMX_HIP(upload(pb->vUnitTin, unitTin));
+  MMX_HIP(upload(pb->vJointTin, cTin));
+  {
+    std::vector<int32_t> gj, gt, gj2, gt2;
+    for (const auto& h : pb->blocks) {
+      for (size_t c = 0; c < h->parent.size(); ++c) {
+        const int32_t j = cj(h->parent[c]), j2 = h->parentB.empty() ? -1 : cj(h->parentB[c]);
+        gj.push_back(j);
+        gt.push_back(cTin[size_t(j)]);
+        gj2.push_back(j2);
+        gt2.push_back(j2 < 0 ? -1 : cTin[size_t(j2)]);
+      }
+    }
+    gj.insert(gj.end(), gj2.begin(), gj2.end());
+    gt.insert(gt.end(), gt2.begin(), gt2.end());
+    MMX_HIP(upload(pb->vGenJoint, gj));
+    MMX_HIP(upload(pb->vGenTin, gt));
+    std::vector<mmx::EllipsoidDev> ed(pb->ellipsoids.size());
+    for (size_t i = 0; i < ed.size(); ++i) {
+      const mmx_ellipsoid_limit& e = pb->ellipsoids[i];
+      std::memcpy(&ed[i], &e, sizeof(e));
+      const int32_t p = cj(e.parent), ep = cj(e.ellipsoid_parent);
+      ed[i].parent = p;
+      ed[i].ellipsoidParent = ep;
+      ed[i].tinParent = cTin[size_t(p)];
+      const bool onChain = cTin[size_t(ep)] <= cTin[size_t(p)] && cTin[size_t(p)] < cTout[size_t(ep)];
+      ed[i].tinStop = onChain ? cTin[size_t(ep)] : -1;
+    }
+    MMX_HIP(upload(pb->vEllipsoids, ed));
+    std::vector<mmx_parameter_limit> lims(pb->limits);
+    auto crow = [&](int32_t row) { return MMX_PARAMS_PER_JOINT * cj(row / MMX_PARAMS_PER_JOINT) + row % MMX_PARAMS_PER_JOINT; };
+    for (mmx_parameter_limit& lm : lims) {
+      if (lm.type == MMX_LIMIT_MINMAX_JOINT || lm.type == MMX_LIMIT_LINEAR_JOINT) {
+        lm.index0 = crow(lm.index0);
+      }
+      if (lm.type == MMX_LIMIT_LINEAR_JOINT) {
+        lm.index1 = crow(lm.index1);
+      }
+    }
+    MMX_HIP(upload(pb->vLimits, lims));
+  }
+  // ---- the one-launch solve's tables by DFS position, and the slots
+  std::vector<int32_t> subSize(nJc), dfsJoint(nJc), loadedPos, posUnitStart(nJc + 1, pb->U);
+  for (int32_t c = 0; c < Jc; ++c) {
+    subSize[size_t(cTin[size_t(c)])] = cTout[size_t(c)] - cTin[size_t(c)];
+    dfsJoint[size_t(cTin[size_t(c)])] = c;
+  }
+  for (int32_t k = 0; k < J; ++k) { // (a dead position carries no unit: the live rows of the CSR are the whole of it)
+    if (posOf[size_t(k)] >= 0) {
+      posUnitStart[size_t(posOf[size_t(k)])] = f.posUnitStart[size_t(k)];
+      if (f.posUnitStart[size_t(k) + 1] > f.posUnitStart[size_t(k)]) {
+        loadedPos.push_back(posOf[size_t(k)]);
+      }
+    }
+  }
+  std::vector<mmx::ColumnSource> vs(slots);
+  for (mmx::ColumnSource& cs : vs) {
+    if (cs.tin == cs.tout || !lj.live[size_t(cs.joint)]) { // a pad slot (weight 0, empty interval): any live joint will do
+      cs = mmx::ColumnSource{0, cs.dof, 0, 0, -1, cs.weight};
+      continue;
+    }
+    const int32_t c = lj.compactOf[size_t(cs.joint)];
+    cs.joint = c;
+    cs.parent = cj(cs.parent);
+    cs.tin = cTin[size_t(c)];
+    cs.tout = cTout[size_t(c)];
+  }
+  MMX_HIP(upload(pb->vSubSize, subSize));
+  MMX_HIP(upload(pb->vDfsJoint, dfsJoint));
+  MMX_HIP(upload(pb->vLoadedPos, loadedPos));
+  MMX_HIP(upload(pb->vPosUnitStart, posUnitStart));
+  MMX_HIP(upload(pb->vSrcs, vs));
+  pb->viewBuilt = true;
+  return MMX_OK;
 }
 
 int32_t uploadProblemTables(mmx_problem* pb) {
@@ -726,6 +1011,10 @@ int32_t uploadProblemTables(mmx_problem* pb) {
     }
     pb->fdev.GT = pb->dev.G + int32_t(pb->ellipsoids.size());
     pb->fdev.genRows = pb->fdev.GT > 0 ? pb->dev.rowsJoint - 3 * pb->U : 0;
+    const int32_t rcView = uploadSolveView(pb, slots);
+    if (rcView != MMX_OK) {
+      return rcView;
+    }
   }
   // Solve list of the explicit-Jacobian solver: an enabled parameter none of whose joint-parameter
   // rows has a constraint below it has a zero column in J, so its step is 0 (H_pp = lambda, g_p = 0)
@@ -865,6 +1154,43 @@ int32_t uploadProblemTables(mmx_problem* pb) {
   }
 
   return MMX_OK;
+}
+
+// What the one-launch solve, its mixed-precision instantiation, the wave route and the tree kernels are launched with: the
+// live-joint view of the problem (uploadSolveView) -- rig, problem and table descriptors TOGETHER, so that a table and a rig
+// can never disagree -- or the full descriptors when nothing is pruned: no view built, switched off (mmx_tuning::
+// joint_pruning), or per-instance rigs / constraint parents set (their arrays are indexed by full joint id).
+// Every host decision (routes, instantiations, LDS budgets) keeps reading the full rig's joint count.
+struct SolveView {
+  mmx::RigDev rig;
+  mmx::ProblemDev pb;
+  mmx::FusedDev fd;
+};
+bool solveViewActive(const mmx_problem* pb) {
+  return pb->viewBuilt && pb->tuning.joint_pruning == 0 && pb->rigDev.instPreRot == nullptr && pb->rigDev.instOffset == nullptr &&
+      pb->dev.instPosParent == nullptr && pb->dev.instOriParent == nullptr;
+}
+SolveView solveView(const mmx_problem* pb) {
+  SolveView v{pb->rigDev, pb->dev, pb->fdev};
+  if (!solveViewActive(pb)) {
+    return v;
+  }
+  v.rig = pb->vRig;
+  v.pb.unitJoint = pb->vUnitJoint.as<int32_t>();
+  v.pb.unitTin = pb->vUnitTin.as<int32_t>();
+  v.pb.jointTin = pb->vJointTin.as<int32_t>();
+  v.pb.genJoint = pb->vGenJoint.as<int32_t>();
+  v.pb.genTin = pb->vGenTin.as<int32_t>();
+  v.pb.ellipsoids = pb->vEllipsoids.as<mmx::EllipsoidDev>();
+  v.pb.limits = pb->vLimits.as<mmx::LimitDev>();
+  v.fd.nnz = pb->vNnz;
+  v.fd.subSize = pb->vSubSize.as<int32_t>();
+  v.fd.dfsJoint = pb->vDfsJoint.as<int32_t>();
+  v.fd.loadedPos = pb->vLoadedPos.as<int32_t>();
+  v.fd.unitJoint = pb->vUnitJoint.as<int32_t>();
+  v.fd.posUnitStart = pb->vPosUnitStart.as<int32_t>();
+  v.fd.srcs = pb->vSrcs.as<mmx::ColumnSourceDev>();
+  return v;
 }
 
 bool fusedUsable(const mmx_problem* pb) {
@@ -1014,6 +1340,34 @@ int32_t mmx_host_elimination_order(const mmx_rig_desc* desc, const uint8_t* enab
   }
   if (num_enabled) {
     *num_enabled = int32_t(t.eliminationList.size());
+  }
+  return MMX_OK;
+}
+
+int32_t mmx_host_live_joints(const mmx_rig_desc* desc, int32_t n, const int32_t* joints, uint8_t* live, int32_t* compact_of, int32_t* num_live) {
+  std::string err;
+  const int32_t rc = mmx::validateRigDesc(desc, err);
+  if (rc != MMX_OK) {
+    return fail(rc, err);
+  }
+  if (n < 0 || (n > 0 && joints == nullptr)) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_host_live_joints: negative count or null joint list");
+  }
+  for (int32_t i = 0; i < n; ++i) {
+    if (joints[i] < 0 || joints[i] >= desc->num_joints) {
+      return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_host_live_joints: joint index out of range");
+    }
+  }
+  mmx::LiveJoints lj;
+  mmx::buildLiveJoints(desc->parent, desc->num_joints, joints, n, lj);
+  if (live) {
+    std::memcpy(live, lj.live.data(), lj.live.size());
+  }
+  if (compact_of) {
+    std::memcpy(compact_of, lj.compactOf.data(), sizeof(int32_t) * lj.compactOf.size());
+  }
+  if (num_live) {
+    *num_live = lj.numLive;
   }
   return MMX_OK;
 }
@@ -1203,56 +1557,17 @@ int32_t mmx_rig_create(const mmx_rig_desc* d, int32_t device, mmx_rig** out) {
   UP(r->dPtOffsets, r->ptOffsets);
   UP(r->dLevelOrder, r->topo.levelOrder);
   UP(r->dLevelStart, r->topo.levelStart);
-  // two-slot ELL copy of the parameter transform (one 16-byte record per joint-parameter row) and
-  // the packed level/parent table of the J-assembly kernel
-  std::vector<int32_t> ell(size_t(R) * 4, 0), jumpParent(size_t(r->J));
-  bool ellOk = true;
-  for (int32_t row = 0; row < R; ++row) {
-    const int32_t k0 = r->ptOuter[row], k1 = r->ptOuter[row + 1];
-    if (k1 - k0 > 2) {
-      ellOk = false;
-      break;
-    }
-    for (int s = 0; s < 2; ++s) {
-      int32_t idx = -1, bits = 0;
-      if (k0 + s < k1) {
-        idx = r->ptInner[k0 + s];
-        std::memcpy(&bits, &r->ptValue[k0 + s], 4);
-      }
-      ell[4 * size_t(row) + 2 * s] = idx;
-      ell[4 * size_t(row) + 2 * s + 1] = bits;
-    }
-  }
-  for (int32_t j = 0; j < r->J; ++j) {
-    jumpParent[j] = ((r->parent[j] + 1) << 16) | (r->parent[j] + 1);
-  }
+  // two-slot ELL copy of the parameter transform, the packed level/parent table of the J-assembly kernel and the records of
+  // the non-empty transform rows (deriveRigTables)
+  const RigDerived rd = deriveRigTables(r->J, r->P, r->parent, r->ptOuter, r->ptInner, r->ptValue, int32_t(r->topo.levelStart.size()) - 1);
+  const bool ellOk = rd.ellOk;
+  const std::vector<int32_t>& rowRec = rd.rowRec;
   if (ellOk) {
-    UP(r->dPtEll, ell);
+    UP(r->dPtEll, rd.ell);
   }
-  UP(r->dJumpParent, jumpParent);
-  // records of the non-empty transform rows (RigDev::ptRowRec)
-  std::vector<int32_t> rowRec;
-  if (R < 65536 && r->P <= 65535) { // (every field of a record is an unsigned 16-bit number: row, rows to the next record, first column, entries)
-    std::vector<int32_t> rows;
-    for (int32_t row = 0; row < R; ++row) {
-      if (r->ptOuter[row + 1] > r->ptOuter[row]) {
-        rows.push_back(row);
-      }
-    }
-    for (size_t t = 0; t < rows.size(); ++t) {
-      const int32_t row = rows[t], next = t + 1 < rows.size() ? rows[t + 1] : R;
-      const int32_t k0 = r->ptOuter[row], cnt = r->ptOuter[row + 1] - k0;
-      if (cnt > 65535 || next - row > 65535) { // (does not fit: no records at all, the kernels walk the CSR)
-        rowRec.clear();
-        break;
-      }
-      int32_t bits = 0;
-      std::memcpy(&bits, &r->ptValue[k0], 4);
-      rowRec.insert(rowRec.end(), {row | ((next - row) << 16), r->ptInner[k0] | (cnt << 16), bits, k0});
-    }
-    if (!rowRec.empty()) {
-      UP(r->dPtRowRec, rowRec);
-    }
+  UP(r->dJumpParent, rd.jumpParent);
+  if (!rowRec.empty()) {
+    UP(r->dPtRowRec, rowRec);
   }
 #undef UP
   mmx::RigDev& dv = r->dev;
@@ -1260,11 +1575,9 @@ int32_t mmx_rig_create(const mmx_rig_desc* d, int32_t device, mmx_rig** out) {
   dv.numRowRec = int32_t(rowRec.size() / 4);
   dv.ptEll = ellOk ? r->dPtEll.as<int4>() : nullptr;
   dv.jumpParent = r->dJumpParent.as<int32_t>();
-  dv.jumpRounds = 0;
-  while ((1 << dv.jumpRounds) < int32_t(r->topo.levelStart.size()) - 1) {
-    ++dv.jumpRounds;
-  }
+  dv.jumpRounds = rd.jumpRounds;
   dv.J = r->J;
+  dv.layoutJ = r->J;
   dv.P = r->P;
   dv.R = R;
   dv.numLevels = int32_t(r->topo.levelStart.size()) - 1;
@@ -1396,6 +1709,9 @@ int32_t mmx_problem_set_tuning(mmx_problem* pb, const mmx_tuning* tuning) {
   if (!(tuning->mixed_tolerance >= 0.f) || tuning->mixed_tolerance > 1e-2f || tuning->mixed_max_cg < 0 || tuning->mixed_max_cg > 64) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_tuning::mixed_tolerance: 0 (default) or (0, 1e-2]; mixed_max_cg: 0 (default) or 1..64");
   }
+  if (tuning->joint_pruning != 0 && tuning->joint_pruning != -1) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_tuning::joint_pruning: 0 (on) or -1 (off)");
+  }
   for (int32_t r : tuning->reserved) {
     if (r != 0) {
       return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_tuning::reserved must be zero");
@@ -1407,6 +1723,13 @@ int32_t mmx_problem_set_tuning(mmx_problem* pb, const mmx_tuning* tuning) {
 
 int32_t mmx_problem_last_route(const mmx_problem* pb) {
   return pb != nullptr ? pb->lastRoute : MMX_ROUTE_AUTO;
+}
+
+int32_t mmx_problem_num_solve_joints(const mmx_problem* pb) {
+  if (pb == nullptr || pb->rig == nullptr) {
+    return 0;
+  }
+  return solveViewActive(pb) ? pb->liveJoints.numLive : pb->rig->J;
 }
 
 int32_t mmx_problem_set_enabled(mmx_problem* pb, const uint8_t* enabled) {
@@ -2072,7 +2395,8 @@ int32_t mmx_debug_tree_normal_equations(mmx_problem* pb, const float* theta_dev,
   MMX_HIP(hipSetDevice(pb->rig->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   MMX_HIP(mmx::zeroAsync(jtj_dev, size_t(pb->B) * size_t(pb->dev.n) * size_t(pb->dev.n) * sizeof(float), s));
-  MMX_HIP(mmx::launchTreeNormalEquations(pb->rigDev, pb->dev, pb->fdev, theta_dev, jtj_dev, jtr_dev, nullptr, nullptr, nullptr, nullptr, nullptr, false, s));
+  const SolveView sv = solveView(pb);
+  MMX_HIP(mmx::launchTreeNormalEquations(sv.rig, sv.pb, sv.fd, theta_dev, jtj_dev, jtr_dev, nullptr, nullptr, nullptr, nullptr, nullptr, false, s));
   return MMX_OK;
 }
 
@@ -2300,7 +2624,8 @@ static int32_t solveMixedImpl(
     clk = pb->sClk.as<long long>();
     MMX_HIP(armPhaseStop(clk, s));
   }
-  MMX_HIP(mmx::launchFusedMixed(pb->rigDev, pb->dev, pb->fdev, theta_dev, fst, fp, sel, pb->B, clk, s));
+  const SolveView sv = solveView(pb);
+  MMX_HIP(mmx::launchFusedMixed(sv.rig, sv.pb, sv.fd, theta_dev, fst, fp, sel, pb->B, clk, s));
   if (clk != nullptr) {
     long long h[32];
     MMX_HIP(hipMemcpyAsync(h, clk, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -2483,7 +2808,8 @@ static int32_t solveF32Impl(
     wp.doLineSearch = o->do_line_search;
     wp.stepRule = o->step_rule;
     MMX_ZONE("wave solve: all iterations in one launch, one wavefront per instance");
-    MMX_HIP(mmx::launchWaveSolve(pb->rigDev, pb->dev, pb->fdev, theta_dev, wst, wp, s));
+    const SolveView sv = solveView(pb);
+    MMX_HIP(mmx::launchWaveSolve(sv.rig, sv.pb, sv.fd, theta_dev, wst, wp, s));
     return MMX_OK;
   }
   const bool forceWide = route == MMX_ROUTE_WIDE;
@@ -2554,7 +2880,8 @@ static int32_t solveF32Impl(
     {
       MMX_ZONE("fused solve: all iterations of GaussNewtonSolverT::doIteration in one launch");
       MMX_HIP(pb->sFusedArgs.ensure(mmx::fusedArgsBytes()));
-      MMX_HIP(mmx::launchFusedSolve(pb->rigDev, pb->dev, pb->fdev, theta_dev, fst, fp, nullptr, nullptr, clk, pb->sFusedArgs.p, s));
+      const SolveView sv = solveView(pb);
+      MMX_HIP(mmx::launchFusedSolve(sv.rig, sv.pb, sv.fd, theta_dev, fst, fp, nullptr, nullptr, clk, pb->sFusedArgs.p, s));
     }
     if (clk != nullptr) {
       long long h[32];
@@ -2697,6 +3024,7 @@ static int32_t solveF32Impl(
       genState = pb->sGenState.as<float>();
     }
   }
+  const SolveView sv = solveView(pb); // (the tree kernels' descriptors; everything else on this route keeps the full rig)
   for (int it = 0; it < o->max_iterations; ++it) { // solver.cpp:89
     sp.iteration = it;
     MMX_ZONE("GaussNewtonSolverT::doIteration");
@@ -2704,7 +3032,7 @@ static int32_t solveF32Impl(
       {
         MMX_ZONE("Get JtJ and JtR");
         MMX_HIP(mmx::launchTreeNormalEquations(
-            pb->rigDev, pb->dev, pb->fdev, theta_dev, pb->sJtj.as<float>(), pb->sJtr.as<float>(), st.done, pb->sErr.as<double>(),
+            sv.rig, sv.pb, sv.fd, theta_dev, pb->sJtj.as<float>(), pb->sJtr.as<float>(), st.done, pb->sErr.as<double>(),
             pb->sTreeState.as<float>(), sp.clk != nullptr ? sp.clk + 8 : nullptr, genState, true, s));
       }
       MMX_ZONE("Dense gauss newton step");
@@ -2716,7 +3044,7 @@ static int32_t solveF32Impl(
             pb->sErr.as<double>(), theta_dev, who, sp, s));
         for (int round = 0; round < sp.refine; ++round) {
           MMX_HIP(mmx::launchTreeRefine(
-              pb->rigDev, pb->dev, pb->fdev, theta_dev, pb->sTreeState.as<float>(), genState, pb->sDvec.as<float>(), pb->sRhoVec.as<float>(), pb->sRefState.as<int32_t>(),
+              sv.rig, sv.pb, sv.fd, theta_dev, pb->sTreeState.as<float>(), genState, pb->sDvec.as<float>(), pb->sRhoVec.as<float>(), pb->sRefState.as<int32_t>(),
               sp.lambda, sp.lambdaPer, s));
           MMX_HIP(mmx::launchCholeskyFinishTiled(
               ds, pb->rig->P, factorScratch, pb->sDvec.as<float>(), pb->sRhoVec.as<float>(), pb->sRefState.as<int32_t>(), pb->sErr.as<double>(),
@@ -2989,7 +3317,8 @@ int32_t mmx_debug_fused_normal_equations(
   fp.minIterations = 1;
   fp.maxIterations = 1;
   fp.refine = 0;
-  MMX_HIP(mmx::launchFusedSolve(pb->rigDev, pb->dev, pb->fdev, pb->sTheta.as<float>(), fst, fp, jtj_dev, jtr_dev, nullptr, nullptr, s));
+  const SolveView sv = solveView(pb);
+  MMX_HIP(mmx::launchFusedSolve(sv.rig, sv.pb, sv.fd, pb->sTheta.as<float>(), fst, fp, jtj_dev, jtr_dev, nullptr, nullptr, s));
   return MMX_OK;
 }
 

@@ -159,6 +159,10 @@ struct RigDev {
   const float* ptValue; // [nnz]
   const float* ptOffsets; // [R]
   int32_t ptOffsetsNonZero; // 0: every entry of ptOffsets is zero (the usual case: the solve kernels then skip the load)
+  // The joint count the LDS layouts and the J-dependent PATH choices of the solve kernels are made for.  = J, except in the
+  // live-joint view of a problem (mmx_capi.hip, solveView): there J counts the joints the loops run over and layoutJ stays the
+  // full rig's count, so that the pruned solve takes the branches (and so the summation order and the bits) of the unpruned one.
+  int32_t layoutJ;
   const int32_t* levelOrder; // [J]
   const int32_t* levelStart; // [numLevels+1]
   // two (parameter index, value bits) pairs per joint-parameter row, index -1 = unused slot; null

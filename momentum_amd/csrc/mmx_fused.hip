@@ -599,7 +599,7 @@ __device__ __forceinline__ double blockErrorD(
 template <class FV, typename YFn>
 __device__ __forceinline__ void mixAdjoint(const FV& fd, const FusedLds& s, const MixLds& m, int J, int NP, int n, int nsrc, int tid, YFn yOf, double* out) {
   double *sub, *slot; // where the subtree sums / the per-slot gradients end up
-  if (size_t(7 * fd.U) <= mixXDoubles(J, nsrc) && size_t(nsrc) <= mixYDoubles(J, 0)) {
+  if (size_t(7 * fd.U) <= mixXDoubles(m.layoutJ, nsrc) && size_t(nsrc) <= mixYDoubles(m.layoutJ, 0)) {
     // one thread per UNIT writes its seven moments (the unit evaluation is the arithmetic of this pass: all units at once instead of
     // a loaded joint's units one after the other), then one thread per (loaded joint, channel) adds the joint's few units
     for (int u = tid; u < fd.U; u += 256) {
@@ -1552,6 +1552,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
   const SolveStateDev& st = kArgLazy ? argsDev->st : stV;
   const FusedParams& fp = kArgLazy ? argsDev->fp : fpV;
   const int J = rig.J, P = rig.P, U = fd.U, n = fd.n, nsrc = fd.nsrc;
+  const int JL = rig.layoutJ; // the carve and the J-dependent path choices below follow it, the loops J (RigDev::layoutJ)
   const int kR = rig.R;
 
   // ---- LDS carve (every offset a multiple of 4 floats); must match fusedLdsBytes().  Round 5: laid out by LIFETIME so that
@@ -1578,8 +1579,9 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
   constexpr bool kLeanOps = kFour;
   constexpr bool kLeanAcc = kFour;
   const int kNnz = fd.nnz;
-  const FusedLayout lay = fusedLayout(NB, J, P, U, nsrc, n, fd.numCells, kRule < 0, kGen ? fd.GT : 0, kGen ? fd.genRows : 0, kTR, 0, kMix);
+  const FusedLayout lay = fusedLayout(NB, JL, P, U, nsrc, n, fd.numCells, kRule < 0, kGen ? fd.GT : 0, kGen ? fd.genRows : 0, kTR, 0, kMix);
   MixLds m{};
+  m.layoutJ = JL;
   {
     float* p = smem;
     auto take = [&](size_t count) {
@@ -1592,15 +1594,15 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     s.mTin = reinterpret_cast<int*>(take(nsrc));
     s.mInfo = reinterpret_cast<int*>(take(nsrc));
     s.mW = take(nsrc);
-    lParent = reinterpret_cast<int*>(take(J));
-    lParentPos = takeS(J);
-    lSubSize = takeS(J);
-    lPosUnitStart = takeS(J + 1);
+    lParent = reinterpret_cast<int*>(take(JL));
+    lParentPos = takeS(JL);
+    lSubSize = takeS(JL);
+    lPosUnitStart = takeS(JL + 1);
     lPosUnits = takeS(U);
     lUnitJoint = takeS(U);
     lSolveList = takeS(n);
-    lDfsJoint = takeS(J);
-    lLoadedPos = takeS(J);
+    lDfsJoint = takeS(JL);
+    lLoadedPos = takeS(JL);
     lColToSolve = takeS(P);
     if (kCsrLds) {
       lPtOuter = reinterpret_cast<int*>(take(kR + 1));
@@ -1609,11 +1611,11 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     }
     if (kMix) { // (theta, joint states, residual rows, g and the step live in double: below)
       s.th = s.js = s.up = s.us = s.ur = s.g = s.d0 = nullptr;
-      m.lo = takeS(J);
-      m.hi = takeS(J);
+      m.lo = takeS(JL);
+      m.hi = takeS(JL);
     } else {
       s.th = take(P);
-      s.js = take(size_t(kJs) * J);
+      s.js = take(size_t(kJs) * JL);
       s.up = take(3 * size_t(U));
       s.ur = take(3 * size_t(U));
       s.us = take(U);
@@ -1635,22 +1637,22 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     arena = take(lay.arenaFloats); // srcT (phases E-G)  |  the refinement's buffers and dfull (phases J-K)
     if (kMix) { // ... | the double scratch X, Y (everywhere else)
       m.X = reinterpret_cast<double*>(arena);
-      m.Y = m.X + mixXDoubles(J, nsrc);
+      m.Y = m.X + mixXDoubles(JL, nsrc);
     }
     s.srcT = arena;
     s.tanOwn = arena, s.jd = arena + lay.t9, s.tanPre = arena + lay.t9, s.dfull = arena + 2 * lay.t9;
     float* region = p;
-    s.fkA = reinterpret_cast<double*>(take(fkBufFloats(J)));
+    s.fkA = reinterpret_cast<double*>(take(fkBufFloats(JL)));
     s.fkB = reinterpret_cast<double*>(p); // over own2 / sub2 (2 kC2 J >= fkBufFloats(J) floats)
-    s.own2 = take(size_t(kC2) * J);
-    s.sub2 = take(size_t(kC2) * J);
+    s.own2 = take(size_t(kC2) * JL);
+    s.sub2 = take(size_t(kC2) * JL);
     s.umom = take(lay.umomFloats);
     s.own1 = region, s.sub1 = s.umom; // phases D-E: over the FK buffer (dead after FK) / the unit moments (dead after the own sums)
     s.L = region;
     if (kMix) { // the double arrays, behind everything else (every offset so far is a multiple of 16 bytes)
-      double* d = reinterpret_cast<double*>(smem + (lay.total - alignUp4(2 * mixPersistentDoubles(J, P, U, NP))));
+      double* d = reinterpret_cast<double*>(smem + (lay.total - alignUp4(2 * mixPersistentDoubles(JL, P, U, NP))));
       m.th = d, d += P;
-      m.js = d, d += size_t(kJsD) * J;
+      m.js = d, d += size_t(kJsD) * JL;
       m.up = d, d += 3 * size_t(U);
       m.uf = d, d += 3 * size_t(U);
       m.us = d, d += U;
@@ -2666,7 +2668,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       }
       __syncthreads();
       // ... summed over each joint's ancestor chain (prefix sums down the tree)
-      if (J <= 256) {
+      if (JL <= 256) {
         // pointer jumping with the running sum and the jump target in registers: per round a thread
         // reads its target's sum and target (slot 7 of the row), then every thread publishes its own
         float acc[7];
@@ -2714,7 +2716,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       // over a dead predecessor): with U <= J the per-unit contributions go where tanOwn was, their per-joint sums where
       // tanPre was, the subtree sums over the contributions, the per-slot gradients over the own sums; with U > J the own
       // sums are formed directly where tanOwn was and the two halves swap roles.
-      const bool unitPath = U <= J;
+      const bool unitPath = U <= JL;
       float* refOwn = unitPath ? arena + lay.t9 : arena;
       float* refSub = unitPath ? arena : arena + lay.t9;
       FusedLds sr = s;
@@ -2769,7 +2771,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       __syncthreads();
       MMX_CLK(18)
       // J^T w per slot in parallel (where the own sums were: consumed), then per column the sum of its slots
-      const bool perSource = nsrc <= kTan * J;
+      const bool perSource = nsrc <= kTan * JL;
       float* perS = refOwn;
       if (perSource) {
         for (int e = tid; e < nsrc; e += 256) {
@@ -3393,10 +3395,11 @@ __global__ void __launch_bounds__(64 * kWaves, kCompact ? 2 : 1) treeNormalEquat
   selectInstanceRig(rig, b);
   selectInstanceWeights(pb, b);
   const int J = rig.J, P = rig.P, U = fd.U, n = fd.n, nsrc = fd.nsrc;
+  const int JL = rig.layoutJ; // the carve (and the launcher's choice of it) follows it, the loops J (RigDev::layoutJ)
   const int NB = (n + 15) >> 4, NP = 16 * NB, T = NB * (NB + 1) / 2;
   static_assert(!kCompact || !kExtraRows, "the compact carve is the plain instantiation's");
   TreeNeLds t;
-  const size_t baseFloats = kCompact ? treeNeCompactLdsFloats(J, P, U, nsrc, &t, smem) : treeNeLdsFloats(J, P, U, nsrc, &t, smem);
+  const size_t baseFloats = kCompact ? treeNeCompactLdsFloats(JL, P, U, nsrc, &t, smem) : treeNeLdsFloats(JL, P, U, nsrc, &t, smem);
   TreeNeExtraLds x{};
   if (kExtraRows) {
     treeNeExtraLdsFloats(P, n, fd.GT, fd.genRows, U, &x, smem + baseFloats);
@@ -3815,7 +3818,7 @@ hipError_t launchTreeNormalEquations(
     float* genState,
     bool tileMajor,
     hipStream_t stream) {
-  const size_t lds = treeNormalEquationsLdsBytes(rig.J, rig.P, fd.U, fd.nsrc, fd.n, fd.GT, fd.genRows);
+  const size_t lds = treeNormalEquationsLdsBytes(rig.layoutJ, rig.P, fd.U, fd.nsrc, fd.n, fd.GT, fd.genRows);
   if (lds > 160 * 1024 - 64) {
     return hipErrorInvalidValue;
   }
@@ -3824,7 +3827,7 @@ hipError_t launchTreeNormalEquations(
     // two workgroups of eight waves per CU when the lifetime-packed carve fits half a CU's LDS (BASELINE configs[4]: 79.7 KB):
     // every phase of this kernel is a latency chain of one workgroup (VALU active 8.5 % of the wave cycles at one workgroup of
     // sixteen waves per CU, profiles/r04_pmc_cfg5.txt) -- a second, independent workgroup fills the waits
-    const size_t compact = treeNeCompactLdsFloats(rig.J, rig.P, fd.U, fd.nsrc, nullptr, nullptr) * sizeof(float);
+    const size_t compact = treeNeCompactLdsFloats(rig.layoutJ, rig.P, fd.U, fd.nsrc, nullptr, nullptr) * sizeof(float);
     if (compact > 0 && compact <= 80 * 1024 - 64) {
       static LdsLimitCache ldsLimitC;
       hipError_t rc = ldsLimitC.ensure(reinterpret_cast<const void*>(treeNormalEquationsKernel<false, 8, true>), compact);
@@ -3926,10 +3929,11 @@ __global__ void __launch_bounds__(64 * kWaves, kWaves == 4 ? 2 : 1) treeRefineKe
   }
   selectInstanceWeights(pb, b);
   const int J = rig.J, P = rig.P, U = fd.U, n = fd.n;
+  const int JL = rig.layoutJ; // the carve and the U <= J path choice follow it, the loops J (RigDev::layoutJ)
   const int NP = (n + 15) & ~15;
   const float lambda = lambdaPer != nullptr ? lambdaPer[b] : lambdaAll;
   TreeRefLds t;
-  treeRefineLdsFloats(J, P, U, n, &t, smem, fd.genRows);
+  treeRefineLdsFloats(JL, P, U, n, &t, smem, fd.genRows);
   const bool hasGen = fd.GT > 0 && genState != nullptr;
   const int gst = srcStrideFor(NP), rowsGp = (fd.genRows + 3) & ~3;
   FusedLds s{};
@@ -4026,7 +4030,7 @@ __global__ void __launch_bounds__(64 * kWaves, kWaves == 4 ? 2 : 1) treeRefineKe
   treeSumT<7, false, kTan, 8>(fv.subSize, fv.loadedPos, fv.numLoaded, s.tanOwn, s.tanPre, J, wave, kWaves, lane);
   __syncthreads();
   // w = r - J d, y = sigma w per unit, then the first-order own sums
-  if (U <= J) {
+  if (U <= JL) {
     for (int u = tid; u < U; u += kT) {
       const float* pre = s.tanPre + kTan * fv.unitPos[u];
       const F3 p{s.up[3 * u], s.up[3 * u + 1], s.up[3 * u + 2]};
@@ -4119,7 +4123,7 @@ hipError_t launchTreeRefine(
     float lambda,
     const float* lambdaPer,
     hipStream_t stream) {
-  const size_t lds = treeRefineLdsBytes(rig.J, rig.P, fd.U, fd.n, fd.genRows);
+  const size_t lds = treeRefineLdsBytes(rig.layoutJ, rig.P, fd.U, fd.n, fd.genRows);
   if (lds > 160 * 1024 - 64) {
     return hipErrorInvalidValue;
   }
@@ -4171,7 +4175,7 @@ static hipError_t launchFusedMode(
     void* argsBuf,
     hipStream_t stream) {
   constexpr bool kFourL = FusedFour<NB, kTR, kGen, kRule>::value; // (fusedSolveKernel's kFour)
-  const size_t lds = fusedLdsBytes(NB, rig.J, rig.P, fd.U, fd.nsrc, fd.n, fd.numCells, kRule < 0, kGen ? fd.GT : 0, kGen ? fd.genRows : 0, kTR, kFourL ? 0 : fusedCsrFloats(rig.J, fd.nnz));
+  const size_t lds = fusedLdsBytes(NB, rig.layoutJ, rig.P, fd.U, fd.nsrc, fd.n, fd.numCells, kRule < 0, kGen ? fd.GT : 0, kGen ? fd.genRows : 0, kTR, kFourL ? 0 : fusedCsrFloats(rig.layoutJ, fd.nnz));
   if (lds > 160 * 1024) {
     return hipErrorInvalidValue;
   }
@@ -4243,7 +4247,7 @@ static hipError_t launchFusedNB(
 // the mixed-precision instantiation (generic rule; by-value arguments)
 template <int NB>
 static hipError_t launchFusedMixedNB(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, float* theta, const SolveStateDev& st, const FusedParams& fp, const MixSelect& sel, int blocks, long long* dbgClk, hipStream_t stream) {
-  const size_t lds = fusedLdsBytes(NB, rig.J, rig.P, fd.U, fd.nsrc, fd.n, fd.numCells, true, 0, 0, false, 0, true);
+  const size_t lds = fusedLdsBytes(NB, rig.layoutJ, rig.P, fd.U, fd.nsrc, fd.n, fd.numCells, true, 0, 0, false, 0, true);
   if (lds > 160 * 1024) {
     return hipErrorInvalidValue;
   }

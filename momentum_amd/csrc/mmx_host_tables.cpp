@@ -361,6 +361,30 @@ int32_t buildFusedTables(
   return MMX_OK;
 }
 
+void buildLiveJoints(const int32_t* parent, int32_t J, const int32_t* joints, int32_t n, LiveJoints& out) {
+  out.live.assign(size_t(J), 0);
+  int32_t count = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    for (int32_t a = joints[i]; a >= 0 && a < J && !out.live[size_t(a)]; a = parent[a]) {
+      out.live[size_t(a)] = 1;
+      ++count;
+    }
+  }
+  if (count == 0) { // nothing referenced: nothing to prune by
+    out.live.assign(size_t(J), 1);
+    count = J;
+  }
+  out.numLive = count;
+  out.compactOf.assign(size_t(J), -1);
+  out.fullOf.clear();
+  for (int32_t j = 0; j < J; ++j) {
+    if (out.live[size_t(j)]) {
+      out.compactOf[size_t(j)] = int32_t(out.fullOf.size());
+      out.fullOf.push_back(j);
+    }
+  }
+}
+
 TileMasks eliminationTileMasks(int32_t n, const std::vector<uint8_t>& related, bool dense) {
   TileMasks m;
   const int32_t NB = (n + 15) / 16;

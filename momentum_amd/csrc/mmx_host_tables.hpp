@@ -138,6 +138,23 @@ bool buildF64AssemblyListHost(
     const HostTables& t, const std::vector<int32_t>& solveList, const int32_t* posParent, int32_t Kp, const int32_t* oriParent, int32_t Ko,
     int32_t unitsPerChunk, F64AssemblyListHost& out);
 
+// The joints a problem's solve can depend on: the ancestors-or-self of every joint it references (constraint parents, both
+// joints of the further blocks and of ellipsoid limits, the joints of joint-parameter limits).  A joint outside that set has
+// no constraint in its subtree: its parameters' columns are structurally zero and no residual reads its state, so the solve
+// kernels run over the live joints only, renumbered.  Both maps are MONOTONE (compactOf in joint index, compactPos in DFS
+// position), so every sum over joints or positions keeps its order -- the pruned solve reproduces the unpruned one bit for bit.
+// Pruning nothing is the identity: with no referenced joint, or with every joint live, all J joints are kept.
+struct LiveJoints {
+  int32_t numLive = 0; // joints kept (J when nothing is pruned)
+  std::vector<uint8_t> live; // [J]
+  std::vector<int32_t> compactOf; // [J] index among the live joints, -1 for a dead one
+  std::vector<int32_t> fullOf; // [numLive] ascending
+  bool identity() const {
+    return numLive == int32_t(live.size());
+  }
+};
+void buildLiveJoints(const int32_t* parent, int32_t J, const int32_t* joints, int32_t n, LiveJoints& out);
+
 // Validates the descriptor the way the reference's constructors / MT_CHECKs do
 // (skeleton.cpp:16-22 parent-before-child; parameter_transform.cpp:112-121 sizes).
 // Returns MMX_OK or an error code with a message in `err`.

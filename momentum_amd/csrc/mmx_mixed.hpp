@@ -45,6 +45,7 @@ struct MixLds {
   double* Y; // [max(8 J, P)]
   int16_t* lo; // [J] by DFS position: first index into loadedPos that lies inside the joint's subtree
   int16_t* hi; // [J] ... one past the last
+  int layoutJ; // RigDev::layoutJ: the joint count X / Y were sized for (mixAdjoint's path choice)
 };
 __host__ __device__ inline size_t mixXDoubles(int J, int nsrc) {
   return size_t(7 * J > nsrc ? 7 * J : nsrc);
