@@ -536,7 +536,8 @@ int32_t mmx_problem_set_instance_parents(
  *                                parameters (kMaxModelParams, momentum/math/types.h:426-429: a rig cannot have more)
  *   MMX_ROUTE_WAVE               one launch, ONE WAVEFRONT per instance (four instances per workgroup, no workgroup barrier in
  *                                the iteration loop), the system in registers and a few KB of LDS: the route for small rigs.
- *                                MMX_ROUTE_AUTO never picks it yet; it is taken only when pinned.  Scope (anything else, pinned,
+ *                                MMX_ROUTE_AUTO never picks it yet; it is taken only when pinned (and by mmx_solve_frames, which
+ *                                runs on it: one wavefront per SEQUENCE of frames).  Scope (anything else, pinned,
  *                                is MMX_ERR_UNSUPPORTED with a message that names the condition, before theta or any output is
  *                                touched):
  *                                  rig          <= MMX_WAVE_MAX_JOINTS joints, any tree shape, any parameter count, per-instance
@@ -784,6 +785,57 @@ int32_t mmx_solve_with_step_history(
     float* parameter_history,
     double* step_history,
     void* stream);
+
+/*
+ * Warm-started frame sequences in ONE launch: the serial per-frame loop of trackPosesForFrames
+ * (marker_tracking/marker_tracker.cpp:905-913: every frame's solve starts from the previous frame's result) for S
+ * independent sequences of F = num_frames frames.  Added without an ABI bump (no struct grows): a library that predates
+ * the function lacks the symbol -- that is the feature probe.
+ *   layout      the problem's batch is B = F x S instances, FRAME-MAJOR: instance f S + s is frame f of sequence s.  Every
+ *               per-instance array keeps its meaning and its indexing by instance: the constraint payload,
+ *               function_weights, per-instance rigs, all outputs, both histories.
+ *   theta_dev   [F][S][P] (DEVICE).  In: the rows of frame 0 hold each sequence's initial parameters; the rows of later
+ *               frames are NOT read.  Out: row f S + s holds frame f's result.
+ *   meaning     frame f of sequence s is solved exactly -- bit for bit, on theta and on every output -- as mmx_solve on
+ *               MMX_ROUTE_WAVE solves instance f S + s, started from the result row of frame f - 1 (f = 0: from the
+ *               caller's row).  Nothing couples the frames except where the initial parameters come from.
+ *   non-finite  a frame whose parameters end non-finite gets MMX_SOLVE_NONFINITE and its result row holds its own initial
+ *               parameters (the driver's revert, tensor_ik.cpp:168-173); the next frame starts from that row.
+ *   disabled parameters carry frame 0's values through every row.
+ *   outputs     as mmx_solve_with_history (NULL to skip), [B] / [B][max_iterations] / [B][max_iterations][P].
+ * One wavefront owns a sequence for all its frames (theta stays in its LDS; no launch, no host work and no wait for the
+ * slowest sequence between frames), so the scope is MMX_ROUTE_WAVE's, see mmx_tuning.  Refusals, all before theta or any
+ * output is touched:
+ *   MMX_ERR_INVALID_ARGUMENT  num_frames < 1, or B is no multiple of num_frames
+ *   MMX_ERR_UNSUPPORTED       a problem or options outside MMX_ROUTE_WAVE's scope (the route's own message); a
+ *                             precision other than MMX_PRECISION_F32; a route pinned to anything but MMX_ROUTE_AUTO or
+ *                             MMX_ROUTE_WAVE
+ * mmx_problem_last_route answers MMX_ROUTE_WAVE afterwards; the routing of the other solve entry points is unchanged
+ * (MMX_ROUTE_AUTO still never picks the wave route there).  Kernels only are enqueued (no memset node, no stream wait):
+ * after one warm-up call the call can be captured into a HIP graph like the other solves.  The _host form copies in,
+ * runs, copies out and synchronises like the other host wrappers.
+ * Problems outside the wave route's scope (the one-launch and wide routes) are out of scope of this entry point for now:
+ * the layout is chosen so that a host-driven form for them can keep it.
+ */
+int32_t mmx_solve_frames(
+    mmx_problem* problem,
+    const mmx_gn_options* options,
+    int32_t num_frames,
+    float* theta_dev,
+    double* final_error,
+    int32_t* iterations,
+    int32_t* status,
+    double* error_history,
+    float* parameter_history,
+    void* stream);
+int32_t mmx_solve_frames_host(
+    mmx_problem* problem,
+    const mmx_gn_options* options,
+    int32_t num_frames,
+    float* theta_host,
+    double* final_error_host,
+    int32_t* iterations_host,
+    int32_t* status_host);
 
 /*
  * Numerical diagnostics of the LAST single-precision solve on this handle (one-launch and wide routes;

@@ -848,6 +848,23 @@ class BatchedGaussNewtonSolver {
     check(mmx_solve_host(fn_->handle(), &opt_, parameters.data(), err.data(), iterations_.data(), status_.data()));
     return err;
   }
+  // Warm-started frame sequences in one launch (mmx_solve_frames; the per-frame loop of marker_tracker.cpp:905-913 for
+  // batch / numFrames independent sequences): the function's batch is numFrames x S elements, FRAME-MAJOR -- element f S + s
+  // carries the constraints of frame f of sequence s.  parameters [numFrames * S * P]: in, the rows of frame 0 (the later rows
+  // are not read); out, every frame's result, frame f solved from the result of frame f - 1.  The one-wavefront route's scope
+  // (include/mmx.h); getIterations() / getStatus() per element as after solve.
+  std::vector<double> solveFrames(std::vector<float>& parameters, size_t numFrames) {
+    fn_->sync();
+    const size_t B = fn_->batchSize(), P = fn_->getNumParameters();
+    if (parameters.size() != B * P) {
+      throw std::runtime_error("momentum_amd: parameters.size() != batch * numParameters"); // solver.cpp:77
+    }
+    std::vector<double> err(B);
+    iterations_.assign(B, 0);
+    status_.assign(B, 0);
+    check(mmx_solve_frames_host(fn_->handle(), &opt_, int32_t(numFrames), parameters.data(), err.data(), iterations_.data(), status_.data()));
+    return err;
+  }
   // SolverT<double>::solve with GaussNewtonSolverT<double> for every element (the reference instantiates its
   // solvers for float and double, gauss_newton_solver.cpp:315-316): parameters [batch * P] in double
   std::vector<double> solve(std::vector<double>& parameters) {

@@ -29,6 +29,7 @@ SYMBOLS = [
     "mmx_problem_set_tuning", "mmx_problem_last_route", "mmx_problem_num_solve_joints",
     "mmx_problem_set_enabled", "mmx_problem_set_constraints", "mmx_problem_set_constraints_sized", "mmx_problem_set_instance_rig", "mmx_problem_set_instance_parents", "mmx_eval_jacobian", "mmx_eval_jacobian_timed", "mmx_debug_store_pattern",
     "mmx_eval_skeleton_state", "mmx_eval_normal_equations", "mmx_solve", "mmx_solve_with_history", "mmx_solve_with_step_history", "mmx_problem_solve_diagnostics", "mmx_solve_f64", "mmx_solve_f64_host", "mmx_solve_host",
+    "mmx_solve_frames", "mmx_solve_frames_host",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
     "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
@@ -90,6 +91,8 @@ def lib() -> C.CDLL:
     L.mmx_solve_f64.argtypes = [vp, C.POINTER(GnOptions), vp, vp, vp, vp, vp, vp]
     L.mmx_solve_host.argtypes = [vp, C.POINTER(GnOptions), vp, vp, vp, vp]
     L.mmx_solve_f64_host.argtypes = [vp, C.POINTER(GnOptions), vp, vp, vp, vp]
+    L.mmx_solve_frames.argtypes = [vp, C.POINTER(GnOptions), i32, vp, vp, vp, vp, vp, vp, vp]
+    L.mmx_solve_frames_host.argtypes = [vp, C.POINTER(GnOptions), i32, vp, vp, vp, vp]
     L.mmx_eval_jacobian_host.argtypes = [vp, vp, vp, vp, vp, i32]
     L.mmx_eval_skeleton_state_host.argtypes = [vp, vp, vp]
     L.mmx_debug_tree_normal_equations.argtypes = [vp, vp, vp, vp, vp]
@@ -665,6 +668,37 @@ class Problem:
             lib().mmx_solve(
                 self._h, C.byref(options), _dev(theta), _dev(outputs["error"]), _dev(outputs["iterations"]),
                 _dev(outputs["status"]), _dev(outputs.get("error_history")), _stream_ptr(),
+            )
+        )  # fmt: skip
+        outputs["theta"] = theta
+        return outputs
+
+
+    def solve_frames(self, theta, options: GnOptions, num_frames: int, want_history: bool = False, outputs=None, want_parameter_history: bool = False):
+        """Warm-started frame sequences in one launch (mmx_solve_frames): the batch is num_frames x S instances, frame-major;
+        frame f of sequence s (instance f S + s) is solved as `solve` on the "wave" route solves it, started from the result
+        row of frame f - 1.  theta: float32 cuda tensor [F, S, P] or [B, P], in place -- in: the rows of frame 0 (the later
+        rows are not read), out: every frame's result.  Returns the same dict as `solve`, indexed by instance."""
+        import torch
+
+        assert isinstance(theta, torch.Tensor) and theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous()
+        assert tuple(theta.shape) == (self.B, self.P) or (theta.dim() == 3 and theta.shape[0] * theta.shape[1] == self.B and theta.shape[2] == self.P), theta.shape
+        if theta.dim() == 3:
+            assert theta.shape[0] == int(num_frames), (theta.shape, num_frames)
+        if outputs is None:
+            outputs = dict(
+                error=torch.empty((self.B,), dtype=torch.float64, device=self.device),
+                iterations=torch.empty((self.B,), dtype=torch.int32, device=self.device),
+                status=torch.empty((self.B,), dtype=torch.int32, device=self.device),
+            )
+            if want_history:
+                outputs["error_history"] = torch.empty((self.B, max(1, options.max_iterations)), dtype=torch.float64, device=self.device)
+        if want_parameter_history and "parameter_history" not in outputs:
+            outputs["parameter_history"] = torch.empty((self.B, max(1, options.max_iterations), self.P), dtype=torch.float32, device=self.device)
+        _check(
+            lib().mmx_solve_frames(
+                self._h, C.byref(options), int(num_frames), _dev(theta), _dev(outputs["error"]), _dev(outputs["iterations"]),
+                _dev(outputs["status"]), _dev(outputs.get("error_history")), _dev(outputs.get("parameter_history")), _stream_ptr(),
             )
         )  # fmt: skip
         outputs["theta"] = theta

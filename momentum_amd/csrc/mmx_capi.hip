@@ -2510,7 +2510,7 @@ static bool mixedUsable(const mmx_problem* pb, const mmx_gn_options* o) {
 
 // MMX_ROUTE_WAVE (mmx_wave.hip, scope table in include/mmx.h): null when the one-wavefront-per-instance solve takes this
 // problem with these options, else the condition it fails (the pinned route then answers MMX_ERR_UNSUPPORTED with it)
-static const char* waveRefusal(const mmx_problem* pb, const mmx_gn_options* o) {
+static const char* waveRefusal(const mmx_problem* pb, const mmx_gn_options* o, bool frames = false) {
   const mmx::ProblemDev& d = pb->dev;
   if (pb->rig->J > MMX_WAVE_MAX_JOINTS) {
     return "MMX_ROUTE_WAVE: more than MMX_WAVE_MAX_JOINTS (64) joints";
@@ -2545,7 +2545,7 @@ static const char* waveRefusal(const mmx_problem* pb, const mmx_gn_options* o) {
   if (o->step_rule != MMX_STEP_GN_FIXED_LAMBDA) {
     return "MMX_ROUTE_WAVE: only MMX_STEP_GN_FIXED_LAMBDA (not the LM schedule, not the trust region)";
   }
-  if (mmx::waveLdsBytes(pb->rig->J, pb->rig->P, pb->U, pb->fdev.n) > 160 * 1024) {
+  if (mmx::waveLdsBytes(pb->rig->J, pb->rig->P, pb->U, pb->fdev.n, frames) > 160 * 1024) { // (frames: one more parameter vector per wave)
     return "MMX_ROUTE_WAVE: the parameter vector does not fit a wave's share of LDS";
   }
   return nullptr;
@@ -3345,6 +3345,121 @@ int32_t mmx_solve_host(
   MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
   MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(float), hipMemcpyHostToDevice));
   rc = mmx_solve(pb, o, pb->sTheta.as<float>(), pb->sFinalErr.as<double>(), pb->sIters.as<int32_t>(), pb->sStatus.as<int32_t>(), nullptr, nullptr);
+  if (rc != MMX_OK) {
+    return rc;
+  }
+  MMX_HIP(hipDeviceSynchronize());
+  MMX_HIP(hipMemcpy(theta_host, pb->sTheta.p, B * P * sizeof(float), hipMemcpyDeviceToHost));
+  if (final_error_host) {
+    MMX_HIP(hipMemcpy(final_error_host, pb->sFinalErr.p, B * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (iterations_host) {
+    MMX_HIP(hipMemcpy(iterations_host, pb->sIters.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  if (status_host) {
+    MMX_HIP(hipMemcpy(status_host, pb->sStatus.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return MMX_OK;
+}
+
+// Frame sequences on the one-wavefront route: the batch is num_frames x S instances, frame-major, and a wave owns a sequence --
+// frame f of sequence s is mmx_solve's MMX_ROUTE_WAVE solve of instance f S + s, started from the result row of frame f - 1.
+// Everything that can refuse is settled before theta or an output is touched; kernels only (zeroAsync is one), as mmx_solve.
+int32_t mmx_solve_frames(
+    mmx_problem* pb,
+    const mmx_gn_options* o,
+    int32_t num_frames,
+    float* theta_dev,
+    double* final_error,
+    int32_t* iterations,
+    int32_t* status,
+    double* error_history,
+    float* parameter_history,
+    void* stream) {
+  MMX_ZONE("mmx_solve_frames (SolverT::solve per frame, warm-started along the sequence)");
+  int32_t rc = checkProblem(pb, true);
+  if (rc != MMX_OK) {
+    return rc;
+  }
+  if (o == nullptr || theta_dev == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "options / theta is null");
+  }
+  if (num_frames < 1 || pb->B % num_frames != 0) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_solve_frames: num_frames must be >= 1 and divide the problem's batch (num_frames x sequences instances, frame-major)");
+  }
+  if (o->max_iterations < 0 || o->min_iterations < 0) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "iteration counts must be >= 0");
+  }
+  if (o->do_line_search != MMX_LINE_SEARCH_NONE && o->do_line_search != MMX_LINE_SEARCH_GAUSS_NEWTON &&
+      o->do_line_search != MMX_LINE_SEARCH_DIRECTIONAL) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "unknown do_line_search rule");
+  }
+  if (o->precision != MMX_PRECISION_F32) {
+    return fail(MMX_ERR_UNSUPPORTED, "mmx_solve_frames runs on MMX_ROUTE_WAVE: only MMX_PRECISION_F32 (not F64 / AUTO / MIXED)");
+  }
+  if (pb->tuning.route != MMX_ROUTE_AUTO && pb->tuning.route != MMX_ROUTE_WAVE) {
+    return fail(MMX_ERR_UNSUPPORTED, "mmx_solve_frames runs on the one-wavefront route only: the handle's route is pinned to another (MMX_ROUTE_AUTO or MMX_ROUTE_WAVE)");
+  }
+  if (const char* why = waveRefusal(pb, o, true)) {
+    return fail(MMX_ERR_UNSUPPORTED, why);
+  }
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  pb->lastRoute = MMX_ROUTE_WAVE;
+  pb->diagValid = false; // (no precision estimate on this route)
+  MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
+  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
+  MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
+  mmx::SolveStateDev wst{};
+  wst.iterations = iterations != nullptr ? iterations : pb->sIters.as<int32_t>();
+  wst.status = status != nullptr ? status : pb->sStatus.as<int32_t>();
+  wst.finalError = final_error != nullptr ? final_error : pb->sFinalErr.as<double>();
+  wst.errorHistory = error_history;
+  wst.paramHistory = parameter_history;
+  if (error_history != nullptr && o->max_iterations > 0) {
+    MMX_HIP(mmx::zeroAsync(error_history, B * size_t(o->max_iterations) * sizeof(double), s));
+  }
+  if (parameter_history != nullptr && o->max_iterations > 0) {
+    MMX_HIP(mmx::zeroAsync(parameter_history, B * size_t(o->max_iterations) * P * sizeof(float), s));
+  }
+  mmx::FusedParams wp{};
+  wp.lambda = o->regularization;
+  wp.threshold = o->threshold;
+  wp.minIterations = o->min_iterations;
+  wp.maxIterations = o->max_iterations;
+  wp.refine = refineSteps(pb);
+  wp.doLineSearch = o->do_line_search;
+  wp.stepRule = o->step_rule;
+  const SolveView sv = solveView(pb);
+  MMX_HIP(mmx::launchWaveFrames(sv.rig, sv.pb, sv.fd, theta_dev, wst, wp, num_frames, s));
+  return MMX_OK;
+}
+
+int32_t mmx_solve_frames_host(
+    mmx_problem* pb,
+    const mmx_gn_options* o,
+    int32_t num_frames,
+    float* theta_host,
+    double* final_error_host,
+    int32_t* iterations_host,
+    int32_t* status_host) {
+  MMX_ZONE("mmx_solve_frames_host");
+  int32_t rc = checkProblem(pb, true);
+  if (rc != MMX_OK) {
+    return rc;
+  }
+  if (theta_host == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "theta is null");
+  }
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  MMX_HIP(pb->sTheta.ensure(B * P * sizeof(float)));
+  MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
+  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
+  MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
+  MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(float), hipMemcpyHostToDevice));
+  rc = mmx_solve_frames(pb, o, num_frames, pb->sTheta.as<float>(), pb->sFinalErr.as<double>(), pb->sIters.as<int32_t>(), pb->sStatus.as<int32_t>(), nullptr, nullptr, nullptr);
   if (rc != MMX_OK) {
     return rc;
   }

@@ -238,8 +238,11 @@ hipError_t launchFusedMixed(
 // the L2 loss, J <= MMX_WAVE_MAX_JOINTS, 1 <= fd.n <= MMX_WAVE_MAX_SOLVED, fd.U <= MMX_WAVE_MAX_UNITS, fixed-lambda Gauss-Newton
 // with or without backtracking (fp.stepRule is not read).  Kernel nodes only.  st: iterations, status, finalError and the two
 // histories are written; diag is not.
-size_t waveLdsBytes(int J, int P, int U, int n); // dynamic LDS of a workgroup
+size_t waveLdsBytes(int J, int P, int U, int n, bool frames = false); // dynamic LDS of a workgroup (frames: launchWaveFrames')
 hipError_t launchWaveSolve(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, float* theta, const SolveStateDev& st, const FusedParams& fp, hipStream_t stream);
+// ... one wavefront per SEQUENCE: pb.B = numFrames x S instances, frame-major; wave s solves s, S + s, 2 S + s, ..., each from the
+// result row of the one before (theta row s: the sequence's initial parameters; the rows of later frames are written, not read)
+hipError_t launchWaveFrames(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, float* theta, const SolveStateDev& st, const FusedParams& fp, int numFrames, hipStream_t stream);
 
 // double-precision solve (mmx_f64.hip)
 size_t solveF64LdsBytes(int J, int P, int U, int n, int G = 0, int genRows = 0);

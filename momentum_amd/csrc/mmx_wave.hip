@@ -18,6 +18,10 @@
 //   K  update: plain step or either backtracking rule (the last trial's joint states and units are the next iteration's)
 // Per-wave LDS: theta, trial theta, joint states, unit vectors / residual rows / scales, the factor (NP x (NP + 4)):
 // 9.5 KB for the 24-joint chain with position + orientation on every joint, 2.1 KB for a 3-joint character.
+//
+// Two translation units are built from this file.  Compiled as it is, it holds waveSolveKernel<16 / 32, false> behind
+// launchWaveSolve (mmx_solve); mmx_wave_frames.hip includes it with MMX_WAVE_FRAMES_UNIT defined and then holds
+// waveSolveKernel<16 / 32, true> behind launchWaveFrames (mmx_solve_frames) and nothing else.
 #include <cfloat>
 
 #include "mmx_kernels.hpp"
@@ -32,12 +36,12 @@ typedef float wf32x4 __attribute__((ext_vector_type(4)));
 constexpr int kWaveThreads = 256; // four instances per workgroup
 
 struct WaveCarve { // offsets in floats inside one wave's share of the workgroup's LDS (every one a multiple of 4)
-  size_t th, tr, js, up, ur, us, utin, L, Linv, total;
+  size_t th, tr, js, up, ur, us, utin, L, Linv, th0, total;
 };
 __host__ __device__ __forceinline__ size_t waveAlign4(size_t v) {
   return (v + 3) & ~size_t(3);
 }
-__host__ __device__ __forceinline__ WaveCarve waveCarve(int NP, int J, int P, int U) {
+__host__ __device__ __forceinline__ WaveCarve waveCarve(int NP, int J, int P, int U, bool frames = false) {
   WaveCarve c;
   size_t p = 0;
   auto take = [&](size_t count) {
@@ -54,6 +58,7 @@ __host__ __device__ __forceinline__ WaveCarve waveCarve(int NP, int J, int P, in
   c.utin = take(size_t(U));
   c.L = take(size_t(NP) * size_t(NP + 4));
   c.Linv = take(size_t(NP));
+  c.th0 = frames ? take(size_t(P)) : 0; // (mmx_solve_frames: the parameters the wave's current frame started from)
   c.total = p;
   return c;
 }
@@ -98,6 +103,8 @@ struct WaveArgs {
   float* paramHistory;
   float lambda, threshold;
   int32_t minIterations, maxIterations, refine, doLineSearch;
+  // frame sequences (waveSolveKernel<NP, true>): S sequences of F frames, instance f S + s = frame f of sequence s
+  int32_t S, F;
 };
 typedef const __attribute__((address_space(4))) WaveArgs* WaveArgsPtr;
 __device__ __forceinline__ WaveArgsPtr waveArgs() {
@@ -411,7 +418,10 @@ __device__ __forceinline__ float waveSolveLLt(const float* L, const float* Linv,
   return bi * invd;
 }
 
-template <int NP>
+// kFrames (mmx_solve_frames): the wave owns SEQUENCE s = the instances s, S + s, 2 S + s, ... and solves them one after the
+// other, each from the result of the one before -- theta stays in the wave's LDS, the problem-shared tables (the column's
+// sources, solveIdx, utin) are loaded once, everything an instance's solve carries is reset per frame.
+template <int NP, bool kFrames>
 __global__ void __launch_bounds__(kWaveThreads) waveSolveKernel(const WaveArgs argsInKernargSegment) {
   (void)argsInKernargSegment; // read through waveArgs()
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -419,12 +429,13 @@ __global__ void __launch_bounds__(kWaveThreads) waveSolveKernel(const WaveArgs a
   constexpr int LS = NP + 4; // row stride of the factor in LDS
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
-  const int b = int(blockIdx.x) * (kWaveThreads / 64) + wave;
-  if (b >= waveArgs()->B) {
+  int b = int(blockIdx.x) * (kWaveThreads / 64) + wave; // (kFrames: the sequence = its frame 0; moves on by S per frame)
+  if (b >= (kFrames ? waveArgs()->S : waveArgs()->B)) {
     return; // (no workgroup barrier anywhere below)
   }
   int P, U, n, Kp;
   float *th, *tr, *js, *up, *ur, *us, *Ls, *Linv;
+  [[maybe_unused]] float* th0 = nullptr; // kFrames: the frame's initial parameters
   int* utin;
   // this lane's column of the system: group h = lane / NP, column c = lane % NP
   const int c = lane & (NP - 1), h = lane / NP;
@@ -434,7 +445,7 @@ __global__ void __launch_bounds__(kWaveThreads) waveSolveKernel(const WaveArgs a
     const WaveArgsPtr A = waveArgs();
     P = A->P, U = A->U, n = A->n, Kp = A->Kp;
     __builtin_assume(U > 0 && n > 0 && P > 0); // (launchWaveSolve refuses anything else)
-    const WaveCarve cv = waveCarve(NP, A->J, P, U);
+    const WaveCarve cv = waveCarve(NP, A->J, P, U, kFrames);
     float* base = smem + size_t(wave) * cv.total;
     th = base + cv.th, tr = base + cv.tr, js = base + cv.js, up = base + cv.up, ur = base + cv.ur, us = base + cv.us;
     utin = reinterpret_cast<int*>(base + cv.utin);
@@ -443,8 +454,16 @@ __global__ void __launch_bounds__(kWaveThreads) waveSolveKernel(const WaveArgs a
     // the compiler derives from them ahead of the loop -- are what spilled)
     asm volatile("" : "+v"(th), "+v"(tr), "+v"(js), "+v"(up), "+v"(ur), "+v"(us), "+v"(utin), "+v"(Ls), "+v"(Linv));
     const float* thg = A->theta + size_t(b) * P;
-    for (int i = lane; i < P; i += 64) {
-      th[i] = thg[i];
+    if constexpr (kFrames) {
+      th0 = base + cv.th0;
+      asm volatile("" : "+v"(th0));
+      for (int i = lane; i < P; i += 64) {
+        th[i] = th0[i] = thg[i];
+      }
+    } else {
+      for (int i = lane; i < P; i += 64) {
+        th[i] = thg[i];
+      }
     }
     const int32_t* unitTin = A->unitTin;
     for (int u = lane; u < U; u += 64) {
@@ -461,266 +480,286 @@ __global__ void __launch_bounds__(kWaveThreads) waveSolveKernel(const WaveArgs a
   const int laneO = lane;
   const ColumnSourceDev s0O = s0;
 
-  double lastError = DBL_MAX; // solver.cpp:84-85
-  double curError = DBL_MAX;
-  int itersDone = 0, status = 0;
-  bool stateValid = false; // js / up / ur / us already belong to th (left by the last trial of a line search)
-  double stateError = 0.0;
+  // one pass = one instance's solve; kFrames: a pass per frame, everything below the loop head is per-frame state (above all
+  // stateValid: the joint states and units a line search left in LDS are the PREVIOUS frame's payload's)
+  for ([[maybe_unused]] int frame = 0;;) {
+    double lastError = DBL_MAX; // solver.cpp:84-85
+    double curError = DBL_MAX;
+    int itersDone = 0, status = 0;
+    bool stateValid = false; // js / up / ur / us already belong to th (left by the last trial of a line search)
+    double stateError = 0.0;
 
-  for (int it = 0; it < waveArgs()->maxIterations; ++it) {
-    // Opaque per-iteration copies of the lane index and of the lane's primary source: what derives from them (lane masks of the
-    // dof tests, addresses) is recomputed where it is used instead of being held in scalar registers across the iteration loop
-    int lane = laneO;
-    asm volatile("" : "+v"(lane));
-    const int c = lane & (NP - 1), h = lane / NP;
-    const bool colLive = c < n;
-    ColumnSourceDev s0 = s0O;
-    asm volatile("" : "+v"(s0.joint), "+v"(s0.dof), "+v"(s0.tin), "+v"(s0.tout), "+v"(s0.parent), "+v"(s0.weight));
-    // the lane's unit of the group round starting at u0 (a unit beyond U: tin -1 and sigma 0 -- no source applies)
-    auto unitAt = [&](int u0, Unit& un, float& sigma, int& ui) {
-      const int u = u0 + h;
-      ui = u < U ? u : U - 1;
-      un.v = F3{up[3 * ui], up[3 * ui + 1], up[3 * ui + 2]};
-      un.isPoint = ui < Kp;
-      un.tin = u < U ? utin[ui] : -1;
-      sigma = u < U ? us[ui] : 0.f;
-    };
-    // total of a per-lane partial over the groups, for the lane's column (the same order in every lane of a column)
-    auto overGroups = [&](float part) {
-      float tot = 0.f;
-  #pragma unroll
-      for (int k = 0; k < G; ++k) {
-        tot += shflF(part, c + k * NP);
-      }
-      return tot;
-    };
-    // ================= A-C
-    if (stateValid) {
-      curError = stateError;
-    } else {
-      waveFk(b, th, js, lane);
-      curError = waveUnits(b, js, up, ur, us, lane);
-    }
-    const float lambda = waveArgs()->lambda;
-    // ================= G: H = J^T J on the matrix cores, g = J^T r
-    float gc;
-    {
-      const ColumnSourceDev* srcs = waveArgs()->srcs;
-      WaveAcc<NP> acc;
-      acc.zero();
-      float gpart = 0.f;
-      for (int u0 = 0; u0 < U; u0 += G) {
-        Unit un;
-        float sigma;
-        int ui;
-        unitAt(u0, un, sigma, ui);
-        const F3 dv = waveColumnDerivative(s0, srcs, x0, x1, js, un);
-        const float jx = sigma * dv.x, jy = sigma * dv.y, jz = sigma * dv.z;
-        acc.add(jx);
-        acc.add(jy);
-        acc.add(jz);
-        gpart += jx * ur[3 * ui] + jy * ur[3 * ui + 1] + jz * ur[3 * ui + 2];
-      }
-      gc = overGroups(gpart);
-      acc.store(Ls, lane);
-    }
-    waveSync();
-    // ================= H: damping (gauss_newton_solver.cpp:248) with the factor's floor (kFactorDamping), Cholesky with the
-    // rows in lanes; the factor goes back to LDS strictly lower triangular, 1 / l_ii beside it
-    bool badPivot = false, floored = false;
-    {
-      int i = c; // (the groups beyond the first factor redundantly)
-      asm volatile("" : "+v"(i)); // (nothing derived from the lane index is to be hoisted out of the iteration loop)
-      const float hii = Ls[i * LS + i];
-      const float trace = waveReduceSumF(lane < n ? hii : 0.f);
-      const float muFactor = fmaxf(lambda, kFactorDamping * trace / float(n > 0 ? n : 1));
-      floored = muFactor > lambda;
-      const float hd = i < n ? hii + muFactor : 1.f; // padded rows / columns form an identity block
-      const float floorRow = kPivotFloor * hd;
-      waveSync();
-      if (lane < NP) {
-        Ls[i * LS + i] = hd;
-      }
-      waveSync();
-      float a[NP];
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        a[k] = Ls[i * LS + k];
-      }
-      waveSync(); // every lane holds its row before the factor overwrites H
-      float rawPivot = 1.f, invd = 0.f; // lane j: d_jj as it came out, 1 / l_jj
-      waveFactorStep<NP, 0>(a, floorRow, rawPivot, invd);
-      badPivot = __builtin_amdgcn_ballot_w64(!(rawPivot > 0.f)) != 0ull;
-      // back to LDS: the rows as they are, then every lane clears its row from the diagonal on (a loop over addresses, not 32
-      // lane masks: those cost an SGPR pair each)
-      if (lane < NP) {
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-          Ls[i * LS + k] = a[k];
+    for (int it = 0; it < waveArgs()->maxIterations; ++it) {
+      // Opaque per-iteration copies of the lane index and of the lane's primary source: what derives from them (lane masks of the
+      // dof tests, addresses) is recomputed where it is used instead of being held in scalar registers across the iteration loop
+      int lane = laneO;
+      asm volatile("" : "+v"(lane));
+      const int c = lane & (NP - 1), h = lane / NP;
+      const bool colLive = c < n;
+      ColumnSourceDev s0 = s0O;
+      asm volatile("" : "+v"(s0.joint), "+v"(s0.dof), "+v"(s0.tin), "+v"(s0.tout), "+v"(s0.parent), "+v"(s0.weight));
+      // the lane's unit of the group round starting at u0 (a unit beyond U: tin -1 and sigma 0 -- no source applies)
+      auto unitAt = [&](int u0, Unit& un, float& sigma, int& ui) {
+        const int u = u0 + h;
+        ui = u < U ? u : U - 1;
+        un.v = F3{up[3 * ui], up[3 * ui + 1], up[3 * ui + 2]};
+        un.isPoint = ui < Kp;
+        un.tin = u < U ? utin[ui] : -1;
+        sigma = u < U ? us[ui] : 0.f;
+      };
+      // total of a per-lane partial over the groups, for the lane's column (the same order in every lane of a column)
+      auto overGroups = [&](float part) {
+        float tot = 0.f;
+    #pragma unroll
+        for (int k = 0; k < G; ++k) {
+          tot += shflF(part, c + k * NP);
         }
-        Linv[i] = invd;
+        return tot;
+      };
+      // ================= A-C
+      if (stateValid) {
+        curError = stateError;
+      } else {
+        waveFk(b, th, js, lane);
+        curError = waveUnits(b, js, up, ur, us, lane);
       }
-      waveSync();
-      if (lane < NP) {
-        for (int k = i; k < NP; ++k) {
-          Ls[i * LS + k] = 0.f;
-        }
-      }
-    }
-    waveSync();
-    // ================= I: the step (every lane of column c holds d_c)
-    float dc = waveSolveLLt<NP>(Ls, Linv, colLive ? gc : 0.f, lane);
-    // ================= J: refinement through J (the rule of fusedSolveKernel phase J)
-    {
-      const int refine = waveArgs()->refine;
-      float prevCorr2 = FLT_MAX;
-      for (int rf = 0; rf < refine; ++rf) {
+      const float lambda = waveArgs()->lambda;
+      // ================= G: H = J^T J on the matrix cores, g = J^T r
+      float gc;
+      {
         const ColumnSourceDev* srcs = waveArgs()->srcs;
-        // The two products of the residual are carried in DOUBLE (the entries of J stay the single-precision ones): a problem with
-        // fewer rows than parameters (BASELINE configs[0]: 9 rows, 31 parameters) amplifies the rounding of rho by 1 / lambda in
-        // the directions J does not determine -- in single precision the committed fixture sat at 1.9e-4 of the double oracle,
-        // the bound being 5e-5
-        double rpart = 0.0;
+        WaveAcc<NP> acc;
+        acc.zero();
+        float gpart = 0.f;
         for (int u0 = 0; u0 < U; u0 += G) {
           Unit un;
           float sigma;
           int ui;
           unitAt(u0, un, sigma, ui);
           const F3 dv = waveColumnDerivative(s0, srcs, x0, x1, js, un);
-          // w = r - J d for the unit's three rows; y = sigma w
-          const double dd = double(dc), sg = double(sigma);
-          const double sx = groupSumD<NP>(dd * double(dv.x)), sy = groupSumD<NP>(dd * double(dv.y)), sz = groupSumD<NP>(dd * double(dv.z));
-          const double yx = sg * (double(ur[3 * ui]) - sg * sx), yy = sg * (double(ur[3 * ui + 1]) - sg * sy), yz = sg * (double(ur[3 * ui + 2]) - sg * sz);
-          rpart += double(dv.x) * yx + double(dv.y) * yy + double(dv.z) * yz;
+          const float jx = sigma * dv.x, jy = sigma * dv.y, jz = sigma * dv.z;
+          acc.add(jx);
+          acc.add(jy);
+          acc.add(jz);
+          gpart += jx * ur[3 * ui] + jy * ur[3 * ui + 1] + jz * ur[3 * ui + 2];
         }
-        double jtw = 0.0;
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-          jtw += shflD(rpart, c + k * NP);
-        }
-        const float cr = waveSolveLLt<NP>(Ls, Linv, colLive ? float(jtw - double(lambda) * double(dc)) : 0.f, lane);
-        const float dn = dc + cr;
-        const bool mine = lane < n;
-        const float corr2 = waveReduceSumF(mine ? cr * cr : 0.f);
-        const float step2 = waveReduceSumF(mine ? dn * dn : 0.f);
-        // a correction is only taken when it is a contraction: otherwise undo it and stop
-        if (corr2 > 0.25f * step2 || corr2 > prevCorr2) {
-          dc = dn - cr;
-          break;
-        }
-        dc = dn;
-        prevCorr2 = corr2;
-        if (!(corr2 > 1e-6f * step2)) {
-          break;
-        }
+        gc = overGroups(gpart);
+        acc.store(Ls, lane);
       }
-    }
-    // ================= K: update (gauss_newton_solver.cpp:283-313, gauss_newton_solver_qr.cpp:126-149)
-    const int doLineSearch = waveArgs()->doLineSearch;
-    if (doLineSearch != 0) {
-      const float scaledError = 1e-3f * float(curError);
-      double gd = 0.0;
-      if (doLineSearch == 2) {
-        gd = double(waveReduceSumF(lane < n ? gc * dc : 0.f));
-      }
-      float scale = 1.f;
-      for (int ls = 0; ls < 10; ++ls) {
-        for (int i = lane; i < P; i += 64) {
-          tr[i] = th[i];
+      waveSync();
+      // ================= H: damping (gauss_newton_solver.cpp:248) with the factor's floor (kFactorDamping), Cholesky with the
+      // rows in lanes; the factor goes back to LDS strictly lower triangular, 1 / l_ii beside it
+      bool badPivot = false, floored = false;
+      {
+        int i = c; // (the groups beyond the first factor redundantly)
+        asm volatile("" : "+v"(i)); // (nothing derived from the lane index is to be hoisted out of the iteration loop)
+        const float hii = Ls[i * LS + i];
+        const float trace = waveReduceSumF(lane < n ? hii : 0.f);
+        const float muFactor = fmaxf(lambda, kFactorDamping * trace / float(n > 0 ? n : 1));
+        floored = muFactor > lambda;
+        const float hd = i < n ? hii + muFactor : 1.f; // padded rows / columns form an identity block
+        const float floorRow = kPivotFloor * hd;
+        waveSync();
+        if (lane < NP) {
+          Ls[i * LS + i] = hd;
         }
         waveSync();
+        float a[NP];
+  #pragma unroll
+        for (int k = 0; k < NP; ++k) {
+          a[k] = Ls[i * LS + k];
+        }
+        waveSync(); // every lane holds its row before the factor overwrites H
+        float rawPivot = 1.f, invd = 0.f; // lane j: d_jj as it came out, 1 / l_jj
+        waveFactorStep<NP, 0>(a, floorRow, rawPivot, invd);
+        badPivot = __builtin_amdgcn_ballot_w64(!(rawPivot > 0.f)) != 0ull;
+        // back to LDS: the rows as they are, then every lane clears its row from the diagonal on (a loop over addresses, not 32
+        // lane masks: those cost an SGPR pair each)
+        if (lane < NP) {
+  #pragma unroll
+          for (int k = 0; k < NP; ++k) {
+            Ls[i * LS + k] = a[k];
+          }
+          Linv[i] = invd;
+        }
+        waveSync();
+        if (lane < NP) {
+          for (int k = i; k < NP; ++k) {
+            Ls[i * LS + k] = 0.f;
+          }
+        }
+      }
+      waveSync();
+      // ================= I: the step (every lane of column c holds d_c)
+      float dc = waveSolveLLt<NP>(Ls, Linv, colLive ? gc : 0.f, lane);
+      // ================= J: refinement through J (the rule of fusedSolveKernel phase J)
+      {
+        const int refine = waveArgs()->refine;
+        float prevCorr2 = FLT_MAX;
+        for (int rf = 0; rf < refine; ++rf) {
+          const ColumnSourceDev* srcs = waveArgs()->srcs;
+          // The two products of the residual are carried in DOUBLE (the entries of J stay the single-precision ones): a problem with
+          // fewer rows than parameters (BASELINE configs[0]: 9 rows, 31 parameters) amplifies the rounding of rho by 1 / lambda in
+          // the directions J does not determine -- in single precision the committed fixture sat at 1.9e-4 of the double oracle,
+          // the bound being 5e-5
+          double rpart = 0.0;
+          for (int u0 = 0; u0 < U; u0 += G) {
+            Unit un;
+            float sigma;
+            int ui;
+            unitAt(u0, un, sigma, ui);
+            const F3 dv = waveColumnDerivative(s0, srcs, x0, x1, js, un);
+            // w = r - J d for the unit's three rows; y = sigma w
+            const double dd = double(dc), sg = double(sigma);
+            const double sx = groupSumD<NP>(dd * double(dv.x)), sy = groupSumD<NP>(dd * double(dv.y)), sz = groupSumD<NP>(dd * double(dv.z));
+            const double yx = sg * (double(ur[3 * ui]) - sg * sx), yy = sg * (double(ur[3 * ui + 1]) - sg * sy), yz = sg * (double(ur[3 * ui + 2]) - sg * sz);
+            rpart += double(dv.x) * yx + double(dv.y) * yy + double(dv.z) * yz;
+          }
+          double jtw = 0.0;
+  #pragma unroll
+          for (int k = 0; k < G; ++k) {
+            jtw += shflD(rpart, c + k * NP);
+          }
+          const float cr = waveSolveLLt<NP>(Ls, Linv, colLive ? float(jtw - double(lambda) * double(dc)) : 0.f, lane);
+          const float dn = dc + cr;
+          const bool mine = lane < n;
+          const float corr2 = waveReduceSumF(mine ? cr * cr : 0.f);
+          const float step2 = waveReduceSumF(mine ? dn * dn : 0.f);
+          // a correction is only taken when it is a contraction: otherwise undo it and stop
+          if (corr2 > 0.25f * step2 || corr2 > prevCorr2) {
+            dc = dn - cr;
+            break;
+          }
+          dc = dn;
+          prevCorr2 = corr2;
+          if (!(corr2 > 1e-6f * step2)) {
+            break;
+          }
+        }
+      }
+      // ================= K: update (gauss_newton_solver.cpp:283-313, gauss_newton_solver_qr.cpp:126-149)
+      const int doLineSearch = waveArgs()->doLineSearch;
+      if (doLineSearch != 0) {
+        const float scaledError = 1e-3f * float(curError);
+        double gd = 0.0;
+        if (doLineSearch == 2) {
+          gd = double(waveReduceSumF(lane < n ? gc * dc : 0.f));
+        }
+        float scale = 1.f;
+        for (int ls = 0; ls < 10; ++ls) {
+          for (int i = lane; i < P; i += 64) {
+            tr[i] = th[i];
+          }
+          waveSync();
+          if (lane < n) {
+            tr[solveIdx] -= scale * dc;
+          }
+          waveSync();
+          waveFk(b, tr, js, lane);
+          stateError = waveUnits(b, js, up, ur, us, lane);
+          if ((curError - stateError) >= (doLineSearch == 2 ? double(1e-4f * scale) * gd : double(scale * scaledError))) {
+            break;
+          }
+          scale *= 0.5f;
+        }
+        for (int i = lane; i < P; i += 64) {
+          th[i] = tr[i];
+        }
+        stateValid = true; // the last trial evaluated IS the new theta
+      } else {
         if (lane < n) {
-          tr[solveIdx] -= scale * dc;
+          th[solveIdx] -= dc; // skeleton_solver_function.cpp:158
         }
-        waveSync();
-        waveFk(b, tr, js, lane);
-        stateError = waveUnits(b, js, up, ur, us, lane);
-        if ((curError - stateError) >= (doLineSearch == 2 ? double(1e-4f * scale) * gd : double(scale * scaledError))) {
+      }
+      waveSync();
+      {
+        const WaveArgsPtr A = waveArgs();
+        const size_t row = size_t(b) * A->maxIterations + it;
+        float* paramHistory = A->paramHistory;
+        if (paramHistory != nullptr) { // solver.cpp:101-106
+          float* ph = asGlobal(paramHistory) + row * size_t(P);
+          for (int i = lane; i < P; i += 64) {
+            ph[i] = th[i];
+          }
+        }
+        double* errorHistory = A->errorHistory;
+        if (errorHistory != nullptr && lane == 0) {
+          asGlobal(errorHistory)[row] = curError;
+        }
+        itersDone = it + 1;
+        status |= badPivot ? 2 : 0; // MMX_SOLVE_NOT_PD
+        status |= floored ? 4 : 0; // MMX_SOLVE_DAMPING_FLOORED
+        // solver.cpp:96-119
+        const bool converged = fabs(lastError - curError) / (fabs(curError) + double(FLT_MIN)) <= double(A->threshold) * double(FLT_EPSILON);
+        lastError = curError;
+        asm volatile("" : "+v"(lastError)); // (kept in vector registers across the iteration: two scalar registers fewer)
+        if (it >= A->minIterations && converged) {
           break;
         }
-        scale *= 0.5f;
-      }
-      for (int i = lane; i < P; i += 64) {
-        th[i] = tr[i];
-      }
-      stateValid = true; // the last trial evaluated IS the new theta
-    } else {
-      if (lane < n) {
-        th[solveIdx] -= dc; // skeleton_solver_function.cpp:158
       }
     }
-    waveSync();
-    {
-      const WaveArgsPtr A = waveArgs();
-      const size_t row = size_t(b) * A->maxIterations + it;
-      float* paramHistory = A->paramHistory;
-      if (paramHistory != nullptr) { // solver.cpp:101-106
-        float* ph = asGlobal(paramHistory) + row * size_t(P);
-        for (int i = lane; i < P; i += 64) {
-          ph[i] = th[i];
-        }
+
+    // NaN / Inf guard of the batched driver: theta in global memory still holds the initial parameters, "revert" = do not write
+    int laneE = laneO; // (an opaque copy: the loop masks below are not the prologue's, held across the whole solve)
+    asm volatile("" : "+v"(laneE));
+    int bad = 0;
+    for (int i = laneE; i < P; i += 64) {
+      bad |= isfinite(th[i]) ? 0 : 1;
+    }
+    const bool anyBad = __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
+    const WaveArgsPtr A = waveArgs();
+    if constexpr (kFrames) {
+      // the frame's row takes its result -- or, reverted, the parameters it started from --, and that is where the next frame starts
+      // (each lane keeps to its own entries of th / th0: no ordering needed among the three)
+      float* thg = asGlobal(A->theta) + size_t(b) * P;
+      for (int i = laneE; i < P; i += 64) {
+        const float v = anyBad ? th0[i] : th[i];
+        th[i] = v, th0[i] = v, thg[i] = v;
       }
-      double* errorHistory = A->errorHistory;
-      if (errorHistory != nullptr && lane == 0) {
-        asGlobal(errorHistory)[row] = curError;
+    } else if (!anyBad) {
+      float* thg = asGlobal(A->theta) + size_t(b) * P;
+      for (int i = laneE; i < P; i += 64) {
+        thg[i] = th[i];
       }
-      itersDone = it + 1;
-      status |= badPivot ? 2 : 0; // MMX_SOLVE_NOT_PD
-      status |= floored ? 4 : 0; // MMX_SOLVE_DAMPING_FLOORED
-      // solver.cpp:96-119
-      const bool converged = fabs(lastError - curError) / (fabs(curError) + double(FLT_MIN)) <= double(A->threshold) * double(FLT_EPSILON);
-      lastError = curError;
-      asm volatile("" : "+v"(lastError)); // (kept in vector registers across the iteration: two scalar registers fewer)
-      if (it >= A->minIterations && converged) {
+    }
+    if (laneE == 0) {
+      asGlobal(A->iterations)[b] = itersDone;
+      asGlobal(A->finalError)[b] = curError;
+      asGlobal(A->status)[b] = anyBad ? 1 : status; // MMX_SOLVE_NONFINITE
+    }
+    if constexpr (kFrames) {
+      if (++frame >= A->F) {
         break;
       }
+      b += A->S;
+      waveSync(); // th is settled before the next frame's forward kinematics reads it
+    } else {
+      break;
     }
-  }
-
-  // NaN / Inf guard of the batched driver: theta in global memory still holds the initial parameters, "revert" = do not write
-  int laneE = laneO; // (an opaque copy: the loop masks below are not the prologue's, held across the whole solve)
-  asm volatile("" : "+v"(laneE));
-  int bad = 0;
-  for (int i = laneE; i < P; i += 64) {
-    bad |= isfinite(th[i]) ? 0 : 1;
-  }
-  const bool anyBad = __builtin_amdgcn_ballot_w64(bad != 0) != 0ull;
-  const WaveArgsPtr A = waveArgs();
-  if (!anyBad) {
-    float* thg = asGlobal(A->theta) + size_t(b) * P;
-    for (int i = laneE; i < P; i += 64) {
-      thg[i] = th[i];
-    }
-  }
-  if (laneE == 0) {
-    asGlobal(A->iterations)[b] = itersDone;
-    asGlobal(A->finalError)[b] = curError;
-    asGlobal(A->status)[b] = anyBad ? 1 : status; // MMX_SOLVE_NONFINITE
   }
 }
 
-template <int NP>
+template <int NP, bool kFrames>
 hipError_t launchWaveNP(const WaveArgs& a, size_t lds, hipStream_t stream) {
   static LdsLimitCache ldsLimit; // (one per instantiation)
-  hipError_t rc = ldsLimit.ensure(reinterpret_cast<const void*>(waveSolveKernel<NP>), lds);
+  hipError_t rc = ldsLimit.ensure(reinterpret_cast<const void*>(waveSolveKernel<NP, kFrames>), lds);
   if (rc != hipSuccess) {
     return rc;
   }
   const int perGroup = kWaveThreads / 64;
-  hipLaunchKernelGGL((waveSolveKernel<NP>), dim3((a.B + perGroup - 1) / perGroup), dim3(kWaveThreads), lds, stream, a);
+  const int waves = kFrames ? a.S : a.B;
+  hipLaunchKernelGGL((waveSolveKernel<NP, kFrames>), dim3((waves + perGroup - 1) / perGroup), dim3(kWaveThreads), lds, stream, a);
   return hipGetLastError();
 }
 
-} // namespace
-
-size_t waveLdsBytes(int J, int P, int U, int n) {
-  return size_t(kWaveThreads / 64) * waveCarve(n <= 16 ? 16 : 32, J, P, U).total * sizeof(float);
-}
-
-hipError_t launchWaveSolve(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, float* theta, const SolveStateDev& st, const FusedParams& fp, hipStream_t stream) {
-  const size_t lds = waveLdsBytes(rig.J, rig.P, fd.U, fd.n);
+// numFrames 0: one wave per instance (mmx_solve); >= 1: one wave per sequence of numFrames frames (mmx_solve_frames)
+template <bool kFrames>
+hipError_t launchWave(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, float* theta, const SolveStateDev& st, const FusedParams& fp, int numFrames, hipStream_t stream) {
+  constexpr bool frames = kFrames;
+  const size_t lds = waveLdsBytes(rig.J, rig.P, fd.U, fd.n, frames);
   if (rig.J > MMX_WAVE_MAX_JOINTS || fd.n > MMX_WAVE_MAX_SOLVED || fd.n <= 0 || fd.U <= 0 || fd.U > MMX_WAVE_MAX_UNITS || lds > 160 * 1024 ||
-      pb.lossPos.type != 0 || pb.lossOri.type != 0 || pb.instPosParent != nullptr || pb.instOriParent != nullptr) {
+      pb.lossPos.type != 0 || pb.lossOri.type != 0 || pb.instPosParent != nullptr || pb.instOriParent != nullptr ||
+      (frames && (pb.B <= 0 || pb.B % numFrames != 0))) {
     return hipErrorInvalidValue;
   }
   WaveArgs a{};
@@ -743,7 +782,26 @@ hipError_t launchWaveSolve(const RigDev& rig, const ProblemDev& pb, const FusedD
   a.errorHistory = st.errorHistory, a.paramHistory = st.paramHistory;
   a.lambda = fp.lambda, a.threshold = fp.threshold;
   a.minIterations = fp.minIterations, a.maxIterations = fp.maxIterations, a.refine = fp.refine, a.doLineSearch = fp.doLineSearch;
-  return fd.n <= 16 ? launchWaveNP<16>(a, lds, stream) : launchWaveNP<32>(a, lds, stream);
+  if constexpr (frames) {
+    a.S = pb.B / numFrames, a.F = numFrames;
+  }
+  return fd.n <= 16 ? launchWaveNP<16, kFrames>(a, lds, stream) : launchWaveNP<32, kFrames>(a, lds, stream);
 }
+
+} // namespace
+
+#ifndef MMX_WAVE_FRAMES_UNIT
+size_t waveLdsBytes(int J, int P, int U, int n, bool frames) {
+  return size_t(kWaveThreads / 64) * waveCarve(n <= 16 ? 16 : 32, J, P, U, frames).total * sizeof(float);
+}
+
+hipError_t launchWaveSolve(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, float* theta, const SolveStateDev& st, const FusedParams& fp, hipStream_t stream) {
+  return launchWave<false>(rig, pb, fd, theta, st, fp, 0, stream);
+}
+#else
+hipError_t launchWaveFrames(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, float* theta, const SolveStateDev& st, const FusedParams& fp, int numFrames, hipStream_t stream) {
+  return numFrames > 0 ? launchWave<true>(rig, pb, fd, theta, st, fp, numFrames, stream) : hipErrorInvalidValue;
+}
+#endif
 
 } // namespace mmx

@@ -640,6 +640,28 @@ class Solver:
         th = out["theta"].cpu().numpy()
         return th[0] if single else th
 
+    def solve_frames(self, model_parameters, num_frames: int):
+        """Warm-started frame sequences in one launch (capi.Problem.solve_frames): model_parameters [F * S, P] (or [F, S, P]),
+        frame-major like the solver function's batched constraints; the rows of frame 0 are the sequences' initial parameters,
+        the later rows are not read.  Returns every frame's result in the shape given; per_iteration_errors as after solve."""
+        fn = self.solver_function
+        shape = np.asarray(model_parameters).shape
+        mp = np.ascontiguousarray(np.asarray(model_parameters, dtype=np.float32).reshape(-1, fn.get_num_parameters()))
+        pb, torch = fn.lower(mp.shape[0])
+        pb.set_enabled(self._enabled if self._enabled is not None else np.ones(fn.get_num_parameters(), np.uint8))
+        if self._route != "auto" or getattr(pb, "_solver_route", "auto") != "auto":
+            pb.set_route(self._route)
+            pb._solver_route = self._route
+        o = self.options
+        opt = GnOptions.make(min_iterations=o.min_iterations, max_iterations=o.max_iterations, threshold=o.threshold,
+                             regularization=getattr(o, "regularization", 0.05), do_line_search=self._line_search_rule if getattr(o, "do_line_search", False) else 0)  # fmt: skip
+        out = pb.solve_frames(torch.from_numpy(mp.copy()).to(pb.device), opt, int(num_frames), want_history=True)
+        it = out["iterations"].cpu().numpy()
+        h = out["error_history"].cpu().numpy()
+        self._iteration_history = {}
+        self._history = [[float(x) for x in h[b, : it[b]]] for b in range(mp.shape[0])]
+        return out["theta"].cpu().numpy().reshape(shape)
+
 
 class GaussNewtonSolver(Solver):
     """GaussNewtonSolverT<float> (solver/gauss_newton_solver.h:67-137) for every element of the batch."""
