@@ -249,204 +249,57 @@ struct mmx_problem {
 
 namespace {
 
-// model parameters that can carry a non-zero Jacobian entry of a limit row
-std::vector<int32_t> limitParameters(const mmx_rig* rig, const mmx_parameter_limit& lm) {
-  std::vector<int32_t> out;
-  auto add = [&](int32_t p) {
-    if (std::find(out.begin(), out.end(), p) == out.end()) {
-      out.push_back(p);
-    }
-  };
-  auto addRow = [&](int32_t row) {
-    for (int32_t k = rig->ptOuter[size_t(row)]; k < rig->ptOuter[size_t(row) + 1]; ++k) {
-      add(rig->ptInner[size_t(k)]);
-    }
-  };
-  switch (lm.type) {
-    case MMX_LIMIT_MINMAX:
-      add(lm.index0);
-      break;
-    case MMX_LIMIT_LINEAR:
-    case MMX_LIMIT_HALFPLANE:
-      add(lm.index0);
-      add(lm.index1);
-      break;
-    case MMX_LIMIT_MINMAX_JOINT:
-      addRow(lm.index0);
-      break;
-    case MMX_LIMIT_LINEAR_JOINT:
-      addRow(lm.index1);
-      addRow(lm.index0);
-      break;
-    default:
-      break;
-  }
-  return out;
-}
-
-// Tables derived from a rig's host arrays: the two-slot ELL copy of the parameter transform (one 16-byte record per
-// joint-parameter row), the packed parent / jump-target table, the records of the non-empty transform rows
-// (RigDev::ptRowRec) and the pointer-jumping round count.  mmx_rig_create builds them for the rig, the live-joint view of a
-// problem for its joints.
-struct RigDerived {
-  std::vector<int32_t> ell, jumpParent, rowRec;
-  bool ellOk = true;
-  int32_t jumpRounds = 0;
-};
-RigDerived deriveRigTables(
-    int32_t J, int32_t P, const std::vector<int32_t>& parent, const std::vector<int32_t>& ptOuter, const std::vector<int32_t>& ptInner,
-    const std::vector<float>& ptValue, int32_t numLevels) {
-  RigDerived o;
-  const int32_t R = MMX_PARAMS_PER_JOINT * J;
-  o.ell.assign(size_t(R) * 4, 0);
-  o.jumpParent.assign(size_t(J), 0);
-  for (int32_t row = 0; row < R; ++row) {
-    const int32_t k0 = ptOuter[size_t(row)], k1 = ptOuter[size_t(row) + 1];
-    if (k1 - k0 > 2) {
-      o.ellOk = false;
-      break;
-    }
-    for (int s = 0; s < 2; ++s) {
-      int32_t idx = -1, bits = 0;
-      if (k0 + s < k1) {
-        idx = ptInner[size_t(k0 + s)];
-        std::memcpy(&bits, &ptValue[size_t(k0 + s)], 4);
-      }
-      o.ell[4 * size_t(row) + 2 * s] = idx;
-      o.ell[4 * size_t(row) + 2 * s + 1] = bits;
-    }
-  }
-  for (int32_t j = 0; j < J; ++j) {
-    o.jumpParent[size_t(j)] = ((parent[size_t(j)] + 1) << 16) | (parent[size_t(j)] + 1);
-  }
-  if (R < 65536 && P <= 65535) { // (every field of a record is an unsigned 16-bit number: row, rows to the next record, first column, entries)
-    std::vector<int32_t> rows;
-    for (int32_t row = 0; row < R; ++row) {
-      if (ptOuter[size_t(row) + 1] > ptOuter[size_t(row)]) {
-        rows.push_back(row);
-      }
-    }
-    for (size_t t = 0; t < rows.size(); ++t) {
-      const int32_t row = rows[t], next = t + 1 < rows.size() ? rows[t + 1] : R;
-      const int32_t k0 = ptOuter[size_t(row)], cnt = ptOuter[size_t(row) + 1] - k0;
-      if (cnt > 65535 || next - row > 65535) { // (does not fit: no records at all, the kernels walk the CSR)
-        o.rowRec.clear();
-        break;
-      }
-      int32_t bits = 0;
-      std::memcpy(&bits, &ptValue[size_t(k0)], 4);
-      o.rowRec.insert(o.rowRec.end(), {row | ((next - row) << 16), ptInner[size_t(k0)] | (cnt << 16), bits, k0});
-    }
-  }
-  while ((1 << o.jumpRounds) < numLevels) {
-    ++o.jumpRounds;
-  }
-  return o;
-}
-
-// The joints the problem references (mmx_host_tables.hpp, LiveJoints): constraint parents, the joints of the further blocks
-// and of ellipsoid limits, the joints of joint-parameter limits.
-std::vector<int32_t> referencedJoints(const mmx_problem* pb) {
-  std::vector<int32_t> ref(pb->posParent);
-  ref.insert(ref.end(), pb->oriParent.begin(), pb->oriParent.end());
+// What the problem references, as the table builders of mmx_host_tables.hpp take it
+mmx::ProblemTopology problemTopology(const mmx_problem* pb) {
+  mmx::ProblemTopology p;
+  p.Kp = pb->Kp;
+  p.Ko = pb->Ko;
+  p.posParent = pb->posParent;
+  p.oriParent = pb->oriParent;
+  p.instPos = pb->instPos;
+  p.instOri = pb->instOri;
+  p.unionPos = pb->unionPos;
+  p.unionOri = pb->unionOri;
   for (const auto& h : pb->blocks) {
-    ref.insert(ref.end(), h->parent.begin(), h->parent.end());
-    ref.insert(ref.end(), h->parentB.begin(), h->parentB.end());
+    p.blocks.push_back(mmx::ProblemTopology::Block{h->type, h->parent, h->parentB});
   }
-  for (const mmx_ellipsoid_limit& e : pb->ellipsoids) {
-    ref.push_back(e.parent);
-    ref.push_back(e.ellipsoid_parent);
-  }
-  for (const mmx_parameter_limit& lm : pb->limits) {
-    if (lm.type == MMX_LIMIT_MINMAX_JOINT || lm.type == MMX_LIMIT_LINEAR_JOINT) {
-      ref.push_back(lm.index0 / MMX_PARAMS_PER_JOINT);
-    }
-    if (lm.type == MMX_LIMIT_LINEAR_JOINT) {
-      ref.push_back(lm.index1 / MMX_PARAMS_PER_JOINT);
-    }
-  }
-  return ref;
+  p.ellipsoids = pb->ellipsoids;
+  p.limits = pb->limits;
+  p.hasModel = pb->dev.hasModel != 0;
+  return p;
 }
 
-// The live-joint view's tables: everything the solve kernels index by joint or by DFS position, REMAPPED from the tables
-// uploadProblemTables has just built (solve list, elimination order, slots, term records and tile structure stay as they are).
-// Off -- the kernels keep the full descriptors -- with per-instance constraint parents (their lists name full joint ids; the
-// per-instance rig arrays are looked at per solve, solveView) and when nothing would be pruned.
-int32_t uploadSolveView(mmx_problem* pb, const std::vector<mmx::ColumnSource>& slots) {
-  const mmx_rig* rig = pb->rig;
+// mmx_ellipsoid_limit + the joint words of JointTables (full or renumbered) = the device record
+std::vector<mmx::EllipsoidDev> packEllipsoids(const std::vector<mmx_ellipsoid_limit>& ellipsoids, const mmx::JointTables& jt) {
+  static_assert(sizeof(mmx_ellipsoid_limit) == 30 * 4 && sizeof(mmx::EllipsoidDev) == 32 * 4, "ellipsoid layouts");
+  std::vector<mmx::EllipsoidDev> ed(ellipsoids.size());
+  for (size_t i = 0; i < ed.size(); ++i) {
+    std::memcpy(&ed[i], &ellipsoids[i], sizeof(mmx_ellipsoid_limit));
+    ed[i].parent = jt.ellParent[i];
+    ed[i].ellipsoidParent = jt.ellEllipsoidParent[i];
+    ed[i].tinParent = jt.ellTinParent[i];
+    ed[i].tinStop = jt.ellTinStop[i];
+  }
+  return ed;
+}
+
+// Uploads the live-joint view's tables (mmx::buildLiveView): what the solve kernels index by joint or by DFS position, over
+// the joints the solve can depend on.  uploadProblemTables builds no view -- the kernels keep the full descriptors -- with
+// per-instance constraint parents (their lists name full joint ids; the per-instance rig arrays are looked at per solve,
+// solveView) and when nothing would be pruned.
+int32_t uploadSolveView(mmx_problem* pb, const mmx::LiveView& lv) {
+  static_assert(sizeof(mmx_parameter_limit) == sizeof(mmx::LimitDev), "limit layouts must match");
   pb->viewBuilt = false;
-  const std::vector<int32_t> ref = referencedJoints(pb);
-  mmx::LiveJoints& lj = pb->liveJoints;
-  mmx::buildLiveJoints(rig->parent.data(), rig->J, ref.data(), int32_t(ref.size()), lj);
-  if (lj.identity() || pb->instPos || pb->instOri) {
-    return MMX_OK;
-  }
-  const mmx::HostTables& t = pb->tables;
-  const mmx::FusedTables& f = pb->fused;
-  const int32_t J = rig->J, Jc = lj.numLive;
-  const size_t nJ = size_t(J), nJc = size_t(Jc), nU = size_t(std::max(pb->U, 1));
-  // ---- the rig over the live joints
-  std::vector<int32_t> parent(nJc), ptOuter(1, 0), ptInner;
-  std::vector<float> preRot(4 * nJc), offset(3 * nJc), ptValue, ptOffsets;
-  for (int32_t c = 0; c < Jc; ++c) {
-    const int32_t j = lj.fullOf[size_t(c)];
-    parent[size_t(c)] = rig->parent[size_t(j)] < 0 ? rig->parent[size_t(j)] : lj.compactOf[size_t(rig->parent[size_t(j)])];
-    std::copy_n(&rig->preRot[4 * size_t(j)], 4, &preRot[4 * size_t(c)]);
-    std::copy_n(&rig->offset[3 * size_t(j)], 3, &offset[3 * size_t(c)]);
-    for (int32_t d = 0; d < MMX_PARAMS_PER_JOINT; ++d) {
-      const size_t row = size_t(MMX_PARAMS_PER_JOINT) * size_t(j) + size_t(d);
-      ptInner.insert(ptInner.end(), rig->ptInner.begin() + rig->ptOuter[row], rig->ptInner.begin() + rig->ptOuter[row + 1]);
-      ptValue.insert(ptValue.end(), rig->ptValue.begin() + rig->ptOuter[row], rig->ptValue.begin() + rig->ptOuter[row + 1]);
-      ptOuter.push_back(int32_t(ptInner.size()));
-      ptOffsets.push_back(rig->ptOffsets[row]);
-    }
-  }
-  // levels and the DFS interval of every live joint in the compact numbering: a live joint's ancestors are live, so its level
-  // is the full rig's, and the live positions keep their order (rank among the live positions)
-  std::vector<int32_t> levelStart, levelOrder(nJc), posOf(nJ, -1), cTin(nJc), cTout(nJc);
-  {
-    int32_t maxLevel = 0;
-    for (int32_t j : lj.fullOf) {
-      maxLevel = std::max(maxLevel, t.level[size_t(j)]);
-    }
-    levelStart.assign(size_t(maxLevel) + 2, 0);
-    for (int32_t j : lj.fullOf) {
-      levelStart[size_t(t.level[size_t(j)]) + 1]++;
-    }
-    for (int32_t l = 0; l <= maxLevel; ++l) {
-      levelStart[size_t(l) + 1] += levelStart[size_t(l)];
-    }
-    std::vector<int32_t> cursor(levelStart.begin(), levelStart.end() - 1);
-    for (int32_t c = 0; c < Jc; ++c) {
-      levelOrder[size_t(cursor[size_t(t.level[size_t(lj.fullOf[size_t(c)])])]++)] = c;
-    }
-    int32_t next = 0;
-    for (int32_t k = 0; k < J; ++k) { // full DFS positions, ascending
-      if (lj.live[size_t(f.dfsJoint[size_t(k)])]) {
-        posOf[size_t(k)] = next++;
-      }
-    }
-    std::vector<int32_t> liveBefore(nJ + 1, 0); // live positions before full position k
-    for (int32_t k = 0; k < J; ++k) {
-      liveBefore[size_t(k) + 1] = liveBefore[size_t(k)] + (posOf[size_t(k)] >= 0 ? 1 : 0);
-    }
-    for (int32_t c = 0; c < Jc; ++c) {
-      const int32_t j = lj.fullOf[size_t(c)];
-      cTin[size_t(c)] = liveBefore[size_t(t.tin[size_t(j)])];
-      cTout[size_t(c)] = liveBefore[size_t(t.tout[size_t(j)])];
-    }
-  }
-  const int32_t numLevels = int32_t(levelStart.size()) - 1;
-  const RigDerived rd = deriveRigTables(Jc, rig->P, parent, ptOuter, ptInner, ptValue, numLevels);
-  MMX_HIP(upload(pb->vParent, parent));
-  MMX_HIP(upload(pb->vPreRot, preRot));
-  MMX_HIP(upload(pb->vOffset, offset));
-  MMX_HIP(upload(pb->vPtOuter, ptOuter));
-  MMX_HIP(upload(pb->vPtInner, ptInner));
-  MMX_HIP(upload(pb->vPtValue, ptValue));
-  MMX_HIP(upload(pb->vPtOffsets, ptOffsets));
-  MMX_HIP(upload(pb->vLevelOrder, levelOrder));
-  MMX_HIP(upload(pb->vLevelStart, levelStart));
+  const mmx::RigDerived& rd = lv.derived;
+  MMX_HIP(upload(pb->vParent, lv.rig.parent));
+  MMX_HIP(upload(pb->vPreRot, lv.rig.preRot));
+  MMX_HIP(upload(pb->vOffset, lv.rig.offset));
+  MMX_HIP(upload(pb->vPtOuter, lv.rig.ptOuter));
+  MMX_HIP(upload(pb->vPtInner, lv.rig.ptInner));
+  MMX_HIP(upload(pb->vPtValue, lv.rig.ptValue));
+  MMX_HIP(upload(pb->vPtOffsets, lv.rig.ptOffsets));
+  MMX_HIP(upload(pb->vLevelOrder, lv.order.levelOrder));
+  MMX_HIP(upload(pb->vLevelStart, lv.order.levelStart));
   if (rd.ellOk) {
     MMX_HIP(upload(pb->vPtEll, rd.ell));
   }
@@ -454,11 +307,23 @@ int32_t uploadSolveView(mmx_problem* pb, const std::vector<mmx::ColumnSource>& s
   if (!rd.rowRec.empty()) {
     MMX_HIP(upload(pb->vPtRowRec, rd.rowRec));
   }
+  MMX_HIP(upload(pb->vUnitJoint, lv.joints.unitJoint));
+  MMX_HIP(upload(pb->vUnitTin, lv.joints.unitTin));
+  MMX_HIP(upload(pb->vJointTin, lv.order.tin));
+  MMX_HIP(upload(pb->vGenJoint, lv.joints.genJoint));
+  MMX_HIP(upload(pb->vGenTin, lv.joints.genTin));
+  MMX_HIP(upload(pb->vEllipsoids, packEllipsoids(pb->ellipsoids, lv.joints)));
+  MMX_HIP(upload(pb->vLimits, lv.limits));
+  MMX_HIP(upload(pb->vSubSize, lv.subSize));
+  MMX_HIP(upload(pb->vDfsJoint, lv.dfsJoint));
+  MMX_HIP(upload(pb->vLoadedPos, lv.loadedPos));
+  MMX_HIP(upload(pb->vPosUnitStart, lv.posUnitStart));
+  MMX_HIP(upload(pb->vSrcs, lv.slots));
   mmx::RigDev& v = pb->vRig;
-  v = rig->dev; // P, ptOffsetsNonZero (a dead row's offset moves nothing the solve reads), layoutJ = the full rig's count
-  v.J = Jc;
-  v.R = MMX_PARAMS_PER_JOINT * Jc;
-  v.numLevels = numLevels;
+  v = pb->rig->dev; // P, ptOffsetsNonZero (a dead row's offset moves nothing the solve reads), layoutJ = the full rig's count
+  v.J = int32_t(lv.rig.parent.size());
+  v.R = MMX_PARAMS_PER_JOINT * v.J;
+  v.numLevels = int32_t(lv.order.levelStart.size()) - 1;
   v.parent = pb->vParent.as<int32_t>();
   v.preRot = pb->vPreRot.as<float>();
   v.offset = pb->vOffset.as<float>();
@@ -475,155 +340,101 @@ int32_t uploadSolveView(mmx_problem* pb, const std::vector<mmx::ColumnSource>& s
   v.jumpRounds = rd.jumpRounds;
   v.instPreRot = nullptr;
   v.instOffset = nullptr;
-  pb->vNnz = ptOuter.back();
-  // ---- the problem's joint-indexed tables
-  auto cj = [&](int32_t j) { return j < 0 ? j : lj.compactOf[size_t(j)]; };
-  std::vector<int32_t> unitJoint(nU, 0), unitTin(nU, 0);
-  for (int32_t u = 0; u < pb->U; ++u) {
-    unitJoint[size_t(u)] = cj(f.unitJoint[size_t(u)]);
-    unitTin[size_t(u)] = cTin[size_t(unitJoint[size_t(u)])];
-  }
-  MMX_HIP(upload(pb->vUnitJoint, unitJoint));
-  MMX_HIP(upload(pb->vUnitTin, unitTin));
-  MMX_HIP(upload(pb->vJointTin, cTin));
-  {
-    std::vector<int32_t> gj, gt, gj2, gt2;
-    for (const auto& h : pb->blocks) {
-      for (size_t c = 0; c < h->parent.size(); ++c) {
-        const int32_t j = cj(h->parent[c]), j2 = h->parentB.empty() ? -1 : cj(h->parentB[c]);
-        gj.push_back(j);
-        gt.push_back(cTin[size_t(j)]);
-        gj2.push_back(j2);
-        gt2.push_back(j2 < 0 ? -1 : cTin[size_t(j2)]);
-      }
-    }
-    gj.insert(gj.end(), gj2.begin(), gj2.end());
-    gt.insert(gt.end(), gt2.begin(), gt2.end());
-    MMX_HIP(upload(pb->vGenJoint, gj));
-    MMX_HIP(upload(pb->vGenTin, gt));
-    std::vector<mmx::EllipsoidDev> ed(pb->ellipsoids.size());
-    for (size_t i = 0; i < ed.size(); ++i) {
-      const mmx_ellipsoid_limit& e = pb->ellipsoids[i];
-      std::memcpy(&ed[i], &e, sizeof(e));
-      const int32_t p = cj(e.parent), ep = cj(e.ellipsoid_parent);
-      ed[i].parent = p;
-      ed[i].ellipsoidParent = ep;
-      ed[i].tinParent = cTin[size_t(p)];
-      const bool onChain = cTin[size_t(ep)] <= cTin[size_t(p)] && cTin[size_t(p)] < cTout[size_t(ep)];
-      ed[i].tinStop = onChain ? cTin[size_t(ep)] : -1;
-    }
-    MMX_HIP(upload(pb->vEllipsoids, ed));
-    std::vector<mmx_parameter_limit> lims(pb->limits);
-    auto crow = [&](int32_t row) { return MMX_PARAMS_PER_JOINT * cj(row / MMX_PARAMS_PER_JOINT) + row % MMX_PARAMS_PER_JOINT; };
-    for (mmx_parameter_limit& lm : lims) {
-      if (lm.type == MMX_LIMIT_MINMAX_JOINT || lm.type == MMX_LIMIT_LINEAR_JOINT) {
-        lm.index0 = crow(lm.index0);
-      }
-      if (lm.type == MMX_LIMIT_LINEAR_JOINT) {
-        lm.index1 = crow(lm.index1);
-      }
-    }
-    MMX_HIP(upload(pb->vLimits, lims));
-  }
-  // ---- the one-launch solve's tables by DFS position, and the slots
-  std::vector<int32_t> subSize(nJc), dfsJoint(nJc), loadedPos, posUnitStart(nJc + 1, pb->U);
-  for (int32_t c = 0; c < Jc; ++c) {
-    subSize[size_t(cTin[size_t(c)])] = cTout[size_t(c)] - cTin[size_t(c)];
-    dfsJoint[size_t(cTin[size_t(c)])] = c;
-  }
-  for (int32_t k = 0; k < J; ++k) { // (a dead position carries no unit: the live rows of the CSR are the whole of it)
-    if (posOf[size_t(k)] >= 0) {
-      posUnitStart[size_t(posOf[size_t(k)])] = f.posUnitStart[size_t(k)];
-      if (f.posUnitStart[size_t(k) + 1] > f.posUnitStart[size_t(k)]) {
-        loadedPos.push_back(posOf[size_t(k)]);
-      }
-    }
-  }
-  std::vector<mmx::ColumnSource> vs(slots);
-  for (mmx::ColumnSource& cs : vs) {
-    if (cs.tin == cs.tout || !lj.live[size_t(cs.joint)]) { // a pad slot (weight 0, empty interval): any live joint will do
-      cs = mmx::ColumnSource{0, cs.dof, 0, 0, -1, cs.weight};
-      continue;
-    }
-    const int32_t c = lj.compactOf[size_t(cs.joint)];
-    cs.joint = c;
-    cs.parent = cj(cs.parent);
-    cs.tin = cTin[size_t(c)];
-    cs.tout = cTout[size_t(c)];
-  }
-  MMX_HIP(upload(pb->vSubSize, subSize));
-  MMX_HIP(upload(pb->vDfsJoint, dfsJoint));
-  MMX_HIP(upload(pb->vLoadedPos, loadedPos));
-  MMX_HIP(upload(pb->vPosUnitStart, posUnitStart));
-  MMX_HIP(upload(pb->vSrcs, vs));
+  pb->vNnz = lv.rig.ptOuter.back();
   pb->viewBuilt = true;
   return MMX_OK;
 }
 
+// Builds every table of the problem on the host (mmx_host_tables.hpp: pure index arithmetic, tested on the CPU), then
+// uploads them and sets the descriptors.  A refusal comes out of the build, before anything on the device has changed.
 int32_t uploadProblemTables(mmx_problem* pb) {
   const mmx_rig* rig = pb->rig;
   MMX_HIP(hipSetDevice(rig->device));
+  // ---- build
   const mmx::HostTables& t = pb->tables;
-  std::vector<int32_t> unitJoint(size_t(std::max(pb->U, 1))), unitTin(size_t(std::max(pb->U, 1)));
-  for (int32_t c = 0; c < pb->Kp; ++c) {
-    unitJoint[c] = pb->posParent[c];
+  const mmx_rig_desc rd = rig->desc();
+  const mmx::ProblemTopology topo = problemTopology(pb);
+  std::string err;
+  const mmx::JointTables jt = mmx::buildJointTables(topo, nullptr, t.tin, t.tout);
+  const mmx::StructureLists sl = mmx::buildStructureLists(&rd, topo);
+  mmx::FusedTables fused;
+  int32_t rc = mmx::buildProblemFusedTables(&rd, t, topo, sl, fused, err);
+  if (rc != MMX_OK) {
+    return fail(rc, err);
   }
-  for (int32_t c = 0; c < pb->Ko; ++c) {
-    for (int k = 0; k < 3; ++k) {
-      unitJoint[pb->Kp + 3 * c + k] = pb->oriParent[c];
-    }
+  const mmx::ColumnProgram cp = mmx::buildColumnProgram(t, fused);
+  const int32_t n = int32_t(fused.solveList.size());
+  const int nbFused = mmx::fusedBlocksFor(n); // -1: beyond the fused instantiations (tables unused then)
+  const mmx::SlotTables st = mmx::buildSlotTables(fused, nbFused > 0 ? nbFused : std::max((n + 15) / 16, 1));
+  mmx::TermRuns runs;
+  rc = mmx::buildTermRuns(fused, st, rig->J, runs, err);
+  if (rc != MMX_OK) {
+    return fail(rc, err);
   }
-  for (int32_t u = 0; u < pb->U; ++u) {
-    unitTin[u] = t.tin[unitJoint[u]];
-  }
+  std::vector<uint32_t> terms, terms16;
+  const size_t rounds = mmx::dealTermRuns(runs, 256, terms), rounds16 = mmx::dealTermRuns(runs, 1024, terms16);
+  mmx::LimitTables lt = mmx::buildLimitTables(&rd, pb->limits, fused.solveList);
+  mmx::ExplicitSolveLists xl = mmx::buildExplicitSolveLists(&rd, t, topo, sl.force);
+  const int32_t G = int32_t(jt.genBlock.size()), NE = int32_t(pb->ellipsoids.size());
+  const bool dense = mmx::tileStructureDense(fused, xl.list, G + NE);
+  mmx::TileMasks tileMasks =
+      mmx::eliminationTileMasks(std::min(n, 512), dense ? std::vector<uint8_t>() : mmx::buildRelatedness(&rd, fused, lt.limitPairs), dense);
+  const std::vector<uint32_t> masks = mmx::packTileMasks(tileMasks);
+  mmx::LiveJoints lj;
+  const std::vector<int32_t> ref = mmx::referencedJoints(topo);
+  mmx::buildLiveJoints(rig->parent.data(), rig->J, ref.data(), int32_t(ref.size()), lj);
+  const bool wantView = !lj.identity() && !pb->instPos && !pb->instOri;
+  const mmx::LiveView lv = wantView ? mmx::buildLiveView(&rd, t, fused, topo, lj, st.slots) : mmx::LiveView{};
+  // ---- the host copies other entry points read
+  pb->fused = std::move(fused);
+  pb->limitPairs = std::move(lt.limitPairs);
+  pb->solveN = int32_t(xl.list.size());
+  pb->solveListV1 = std::move(xl.list);
+  pb->solveListF64 = std::move(xl.sorted);
+  pb->f64ListUnitsPerChunk = 0;
+  pb->tileMasks = std::move(tileMasks);
+  pb->liveJoints = std::move(lj);
+  const mmx::FusedTables& f = pb->fused;
+  // ---- upload
   static_assert(sizeof(mmx::ColumnSource) == sizeof(mmx::ColumnSourceDev), "ColumnSource layouts must match");
-  MMX_HIP(upload(pb->dUnitJoint, unitJoint));
-  MMX_HIP(upload(pb->dUnitTin, unitTin));
+  static_assert(sizeof(mmx::JacRec) == sizeof(mmx::JacRecDev) && sizeof(mmx::JacRec) == 32, "JacRec layouts must match");
+  MMX_HIP(upload(pb->dUnitJoint, jt.unitJoint));
+  MMX_HIP(upload(pb->dUnitTin, jt.unitTin));
   MMX_HIP(upload(pb->dJointTin, t.tin));
-  pb->dev.jointTin = pb->dJointTin.as<int32_t>();
-  {
-    // flattened constraints [G], then [G] second joints: the B joint of a pair constraint, -1 for every other type
-    std::vector<int32_t> gj, gt, gb, gj2, gt2;
-    for (size_t i = 0; i < pb->blocks.size(); ++i) {
-      const mmx_problem::JointBlockHost& h = *pb->blocks[i];
-      for (size_t c = 0; c < h.parent.size(); ++c) {
-        const int32_t j = h.parent[c], j2 = h.parentB.empty() ? -1 : h.parentB[c];
-        gj.push_back(j);
-        gt.push_back(t.tin[size_t(j)]);
-        gb.push_back(int32_t(i));
-        gj2.push_back(j2);
-        gt2.push_back(j2 < 0 ? -1 : t.tin[size_t(j2)]);
-      }
-    }
-    const size_t G = gb.size();
-    gj.insert(gj.end(), gj2.begin(), gj2.end());
-    gt.insert(gt.end(), gt2.begin(), gt2.end());
-    MMX_HIP(upload(pb->dGenJoint, gj));
-    MMX_HIP(upload(pb->dGenTin, gt));
-    MMX_HIP(upload(pb->dGenBlock, gb));
-    MMX_HIP(upload(pb->dBlocks, pb->blockDev));
-    pb->dev.numBlocks = int32_t(pb->blocks.size());
-    pb->dev.G = int32_t(G);
-    pb->dev.blocks = pb->dBlocks.as<mmx::JointBlockDev>();
-    pb->dev.genJoint = pb->dGenJoint.as<int32_t>();
-    pb->dev.genTin = pb->dGenTin.as<int32_t>();
-    pb->dev.genBlock = pb->dGenBlock.as<int32_t>();
-    std::vector<mmx::EllipsoidDev> ed(pb->ellipsoids.size());
-    for (size_t i = 0; i < ed.size(); ++i) {
-      const mmx_ellipsoid_limit& e = pb->ellipsoids[i];
-      static_assert(sizeof(mmx_ellipsoid_limit) == 30 * 4 && sizeof(mmx::EllipsoidDev) == 32 * 4, "ellipsoid layouts");
-      std::memcpy(&ed[i], &e, sizeof(e));
-      ed[i].tinParent = t.tin[size_t(e.parent)];
-      const bool onChain = t.tin[size_t(e.ellipsoid_parent)] <= t.tin[size_t(e.parent)] && t.tin[size_t(e.parent)] < t.tout[size_t(e.ellipsoid_parent)];
-      ed[i].tinStop = onChain ? t.tin[size_t(e.ellipsoid_parent)] : -1;
-    }
-    MMX_HIP(upload(pb->dEllipsoids, ed));
-    pb->dev.NE = int32_t(ed.size());
-    pb->dev.ellipsoids = pb->dEllipsoids.as<mmx::EllipsoidDev>();
-  }
+  MMX_HIP(upload(pb->dGenJoint, jt.genJoint));
+  MMX_HIP(upload(pb->dGenTin, jt.genTin));
+  MMX_HIP(upload(pb->dGenBlock, jt.genBlock));
+  MMX_HIP(upload(pb->dBlocks, pb->blockDev));
+  MMX_HIP(upload(pb->dEllipsoids, packEllipsoids(pb->ellipsoids, jt)));
   MMX_HIP(upload(pb->dColStart, t.colStart));
   MMX_HIP(upload(pb->dColSources, t.colSources));
   MMX_HIP(upload(pb->dEnabledList, t.enabledList));
+  MMX_HIP(upload(pb->dEnabledMask, t.enabled));
+  MMX_HIP(upload(pb->dJacRecs, cp.recs));
+  MMX_HIP(upload(pb->dMultiCols, cp.multi));
+  MMX_HIP(upload(pb->dZeroCols, cp.zero));
+  MMX_HIP(upload(pb->dSubSize, f.subSize));
+  MMX_HIP(upload(pb->dDfsJoint, f.dfsJoint));
+  MMX_HIP(upload(pb->dLoadedPos, st.loadedPos));
+  MMX_HIP(upload(pb->dPosUnitStart, f.posUnitStart));
+  MMX_HIP(upload(pb->dPosUnits, f.posUnits));
+  MMX_HIP(upload(pb->dSolveList, f.solveList));
+  MMX_HIP(upload(pb->dSrcStart, st.xStart));
+  MMX_HIP(upload(pb->dSrcs, st.slots));
+  MMX_HIP(upload(pb->dComb, runs.comb));
+  MMX_HIP(upload(pb->dTerms, terms));
+  MMX_HIP(upload(pb->dTerms16, terms16));
+  MMX_HIP(upload(pb->dPairCols, lt.pairCols));
+  MMX_HIP(upload(pb->dLimStart, lt.limStart));
+  MMX_HIP(upload(pb->dLimOf, lt.limOf));
+  MMX_HIP(upload(pb->dPairDest, lt.pairDest));
+  MMX_HIP(upload(pb->dPairStart, lt.pairStart));
+  MMX_HIP(upload(pb->dPairLim, lt.pairLim));
+  MMX_HIP(upload(pb->dSolveListV1, pb->solveListV1));
+  MMX_HIP(upload(pb->dSolveListF64, pb->solveListF64));
+  MMX_HIP(upload(pb->dTileMasks, masks));
+  MMX_HIP(upload(pb->dTileList, pb->tileMasks.tiles));
+  // ---- descriptors
   mmx::ProblemDev& d = pb->dev;
   d.B = pb->B;
   d.Kp = pb->Kp;
@@ -633,527 +444,64 @@ int32_t uploadProblemTables(mmx_problem* pb) {
   d.n = int32_t(t.enabledList.size());
   d.unitJoint = pb->dUnitJoint.as<int32_t>();
   d.unitTin = pb->dUnitTin.as<int32_t>();
+  d.jointTin = pb->dJointTin.as<int32_t>();
+  d.numBlocks = int32_t(pb->blocks.size());
+  d.G = G;
+  d.blocks = pb->dBlocks.as<mmx::JointBlockDev>();
+  d.genJoint = pb->dGenJoint.as<int32_t>();
+  d.genTin = pb->dGenTin.as<int32_t>();
+  d.genBlock = pb->dGenBlock.as<int32_t>();
+  d.NE = NE;
+  d.ellipsoids = pb->dEllipsoids.as<mmx::EllipsoidDev>();
   d.colStart = pb->dColStart.as<int32_t>();
   d.colSources = pb->dColSources.as<mmx::ColumnSourceDev>();
   d.enabledList = pb->dEnabledList.as<int32_t>();
-  {
-    std::vector<uint8_t> mask(size_t(rig->P), 0);
-    for (int32_t p : t.enabledList) {
-      mask[size_t(p)] = 1;
-    }
-    MMX_HIP(upload(pb->dEnabledMask, mask));
-    d.enabledMask = pb->dEnabledMask.as<uint8_t>();
-    d.rowsJoint = 3 * pb->U + pb->genRows + 3 * int32_t(pb->ellipsoids.size());
-  }
-  static_assert(sizeof(mmx::JacRec) == sizeof(mmx::JacRecDev) && sizeof(mmx::JacRec) == 32, "JacRec layouts must match");
-  MMX_HIP(upload(pb->dJacRecs, t.jacRecs));
-  MMX_HIP(upload(pb->dMultiCols, t.multiCols));
-  MMX_HIP(upload(pb->dZeroCols, t.zeroCols));
+  d.enabledMask = pb->dEnabledMask.as<uint8_t>();
+  d.rowsJoint = 3 * pb->U + pb->genRows + 3 * NE;
   d.jacRecs = pb->dJacRecs.as<mmx::JacRecDev>();
   d.multiCols = pb->dMultiCols.as<int32_t>();
   d.zeroCols = pb->dZeroCols.as<int32_t>();
-  d.numJacRecs = int32_t(t.jacRecs.size());
-  d.numMultiCols = int32_t(t.multiCols.size());
-  d.numZeroCols = int32_t(t.zeroCols.size());
-  // tables of the fused solve kernel
-  {
-    const mmx_rig_desc rd = rig->desc();
-    std::string err;
-    // parameters touched by a limit or (all of them) by the model-parameter block stay in the solve list
-    std::vector<uint8_t> force(size_t(rig->P), pb->dev.hasModel ? 1 : 0);
-    for (const mmx_parameter_limit& lm : pb->limits) {
-      for (int32_t p : limitParameters(rig, lm)) {
-        force[size_t(p)] = 1;
-      }
-    }
-    // joints that carry a further joint error function or an ellipsoid limit count like constrained joints for the
-    // structure (solve list, source slots): point-like ones (projection, distance and BOTH joints of a pair among them) see every dof above them,
-    // fixed-axis ones rotations only
-    std::vector<int32_t> structPos, structOri;
-    if (pb->instPos) {
-      structPos = pb->unionPos;
-    }
-    if (pb->instOri) {
-      structOri = pb->unionOri;
-    }
-    for (const auto& h : pb->blocks) {
-      const bool fixedAxis = h->type == MMX_JC_FIXED_AXIS_DIFF || h->type == MMX_JC_FIXED_AXIS_COS || h->type == MMX_JC_FIXED_AXIS_ANGLE;
-      for (int32_t j : h->parent) {
-        (fixedAxis ? structOri : structPos).push_back(j);
-      }
-      structPos.insert(structPos.end(), h->parentB.begin(), h->parentB.end()); // a pair row also walks the chain above its second point
-    }
-    for (const mmx_ellipsoid_limit& e : pb->ellipsoids) {
-      structPos.push_back(e.parent);
-    }
-    const int32_t rc = mmx::buildFusedTables(
-        &rd, t, pb->Kp, pb->posParent.data(), pb->Ko, pb->oriParent.data(), force.data(), structPos.empty() ? nullptr : &structPos,
-        structOri.empty() ? nullptr : &structOri, pb->fused, err);
-    if (rc != MMX_OK) {
-      return fail(rc, err);
-    }
-    const mmx::FusedTables& f = pb->fused;
-    // Column program of the J-assembly kernel, specialised to this problem: a column whose sources
-    // have no constraint vector below them (or that is disabled) is structurally zero -- it moves
-    // to the zero list, which the kernel writes BEFORE forward kinematics (those stores overlap the
-    // FK prologue and cost no arithmetic); the rest as in buildHostTables.
-    {
-      std::vector<mmx::JacRec> recs;
-      std::vector<int32_t> multi, zero;
-      for (int32_t p = 0; p < rig->P; ++p) {
-        const int32_t cnt = t.colStart[size_t(p) + 1] - t.colStart[size_t(p)];
-        if (cnt == 0 || !f.structNonZero[size_t(p)]) {
-          zero.push_back(p);
-          continue;
-        }
-        const mmx::ColumnSource& cs = t.colSources[size_t(t.colStart[size_t(p)])];
-        if (cnt == 1 && cs.dof >= 3 && cs.dof < 6) {
-          recs.push_back(mmx::JacRec{cs.joint, cs.dof, p, cs.tin, cs.tout, cs.parent, cs.weight, 1});
-        } else {
-          multi.push_back(p);
-        }
-      }
-      std::stable_sort(recs.begin(), recs.end(), [](const mmx::JacRec& a, const mmx::JacRec& b) {
-        return a.joint != b.joint ? a.joint < b.joint : a.dof < b.dof;
-      });
-      while (!recs.empty() && recs.size() % 4 != 0) {
-        recs.push_back(recs.back());
-      }
-      MMX_HIP(upload(pb->dJacRecs, recs));
-      MMX_HIP(upload(pb->dMultiCols, multi));
-      MMX_HIP(upload(pb->dZeroCols, zero));
-      d.jacRecs = pb->dJacRecs.as<mmx::JacRecDev>();
-      d.multiCols = pb->dMultiCols.as<int32_t>();
-      d.zeroCols = pb->dZeroCols.as<int32_t>();
-      d.numJacRecs = int32_t(recs.size());
-      d.numMultiCols = int32_t(multi.size());
-      d.numZeroCols = int32_t(zero.size());
-    }
-    MMX_HIP(upload(pb->dSubSize, f.subSize));
-    MMX_HIP(upload(pb->dDfsJoint, f.dfsJoint));
-    std::vector<int32_t> loadedPos;
-    for (int32_t k = 0; k < rig->J; ++k) {
-      if (f.posUnitStart[k + 1] > f.posUnitStart[k]) {
-        loadedPos.push_back(k);
-      }
-    }
-    MMX_HIP(upload(pb->dLoadedPos, loadedPos));
-    MMX_HIP(upload(pb->dPosUnitStart, f.posUnitStart));
-    MMX_HIP(upload(pb->dPosUnits, f.posUnits));
-    MMX_HIP(upload(pb->dSolveList, f.solveList));
-    // Source SLOTS of the fused kernel.  Column c of the compacted system keeps its first source in slot c
-    // (the "primary" source: with it alone the slot index IS the column index, so the 16 x 16 tiles of
-    // H = J^T J come straight out of matrix-core products of the per-slot moment contractions, phase G);
-    // slots n .. NP-1 pad the last block (weight 0); the further sources of multi-source columns (shared
-    // parameters) follow from slot NP on, in column order: extras of column c = slots
-    // NP + xStart[c] .. NP + xStart[c+1] - 1.  (Integer bookkeeping, host side.)
-    const int nbFused = mmx::fusedBlocksFor(int32_t(f.solveList.size())); // -1: beyond the fused instantiations (tables unused then)
-    const int nbSlots = nbFused > 0 ? nbFused : std::max((int32_t(f.solveList.size()) + 15) / 16, 1);
-    const int32_t NPs = 16 * nbSlots;
-    std::vector<mmx::ColumnSource> slots(size_t(NPs), mmx::ColumnSource{0, 3, 0, 0, -1, 0.f});
-    std::vector<int32_t> xStart(size_t(NPs) + 1, 0);
-    std::vector<int32_t> slotOf(f.srcs.size(), -1), slotColumn; // source e -> slot ; slot -> column
-    {
-      const int32_t ncol = int32_t(f.solveList.size());
-      slotColumn.assign(size_t(NPs), -1);
-      for (int32_t c = 0; c < ncol; ++c) {
-        xStart[size_t(c)] = int32_t(slots.size()) - NPs;
-        for (int32_t e = f.srcStart[size_t(c)]; e < f.srcStart[size_t(c) + 1]; ++e) {
-          if (e == f.srcStart[size_t(c)]) {
-            slots[size_t(c)] = f.srcs[size_t(e)];
-            slotOf[size_t(e)] = c;
-            slotColumn[size_t(c)] = c;
-          } else {
-            slotOf[size_t(e)] = int32_t(slots.size());
-            slotColumn.push_back(c);
-            slots.push_back(f.srcs[size_t(e)]);
-          }
-        }
-      }
-      for (int32_t c = ncol; c <= NPs; ++c) {
-        xStart[size_t(c)] = int32_t(slots.size()) - NPs;
-      }
-      while (slots.size() % 4 != 0) {
-        slots.push_back(mmx::ColumnSource{0, 3, 0, 0, -1, 0.f});
-        slotColumn.push_back(-1);
-      }
-    }
-    MMX_HIP(upload(pb->dSrcStart, xStart));
-    MMX_HIP(upload(pb->dSrcs, slots));
-    mmx::FusedDev& fd = pb->fdev;
-    fd.U = pb->U;
-    fd.Kp = pb->Kp;
-    fd.n = int32_t(f.solveList.size());
-    fd.nsrc = int32_t(slots.size());
-    fd.slotBase = NPs;
-    fd.nnz = rig->ptOuter.back();
-    fd.subSize = pb->dSubSize.as<int32_t>();
-    fd.dfsJoint = pb->dDfsJoint.as<int32_t>();
-    fd.loadedPos = pb->dLoadedPos.as<int32_t>();
-    fd.numLoaded = int32_t(loadedPos.size());
-    fd.unitJoint = pb->dUnitJoint.as<int32_t>();
-    fd.posUnitStart = pb->dPosUnitStart.as<int32_t>();
-    fd.posUnits = pb->dPosUnits.as<int32_t>();
-    fd.solveList = pb->dSolveList.as<int32_t>();
-    fd.srcStart = pb->dSrcStart.as<int32_t>();
-    fd.srcs = pb->dSrcs.as<mmx::ColumnSourceDev>();
-    // Structural term records of H for the pairs the matrix-core pass does not cover: entry (row, col),
-    // row >= col, receives one term per pair (source a of row, source c of col) whose joints are in an
-    // ancestor relation AND of which at least one is an extra source; the deeper source supplies the
-    // moment contractions, the other one alpha / B (mmx_fused.hip phase G; weights are folded into the
-    // per-slot tables, the record's weight word stays 1).  Entries are dealt to the 256 threads of a
-    // workgroup in contiguous runs of roughly equal term count; a thread's records are stored interleaved
-    // (record k of thread t at [k * 256 + t]) so that a wave reads them coalesced.
-    {
-      struct Term {
-        uint32_t deep, anc;
-        float w;
-      };
-      struct Entry {
-        int32_t dest;
-        std::vector<Term> terms;
-      };
-      std::vector<Entry> entries;
-      for (int32_t row = 0; row < fd.n; ++row) {
-        for (int32_t col = 0; col <= row; ++col) {
-          Entry en;
-          for (int32_t er = f.srcStart[row]; er < f.srcStart[row + 1]; ++er) {
-            for (int32_t ec = f.srcStart[col]; ec < f.srcStart[col + 1]; ++ec) {
-              if (er == f.srcStart[row] && ec == f.srcStart[col]) {
-                continue; // primary x primary: the matrix-core pass
-              }
-              const mmx::ColumnSource &sa = f.srcs[er], &sc = f.srcs[ec];
-              int32_t deep, anc;
-              if (sc.tin <= sa.tin && sa.tin < sc.tout) {
-                deep = slotOf[size_t(er)], anc = slotOf[size_t(ec)];
-              } else if (sa.tin <= sc.tin && sc.tin < sa.tout) {
-                deep = slotOf[size_t(ec)], anc = slotOf[size_t(er)];
-              } else {
-                continue;
-              }
-              en.terms.push_back(Term{uint32_t(deep), uint32_t(anc), 1.f});
-            }
-          }
-          if (en.terms.empty()) {
-            continue;
-          }
-          const int I = row >> 4, Jc = col >> 4, r = row & 15, c = col & 15;
-          const int t = I * (I + 1) / 2 + Jc;
-          en.dest = t * 256 + r * 16 + ((((c >> 2) ^ (r >> 2)) & 3) << 2) + (c & 3); // tileAddr()
-          entries.push_back(std::move(en));
-        }
-      }
-      if (fd.nsrc >= (1 << 12)) {
-        return fail(MMX_ERR_UNSUPPORTED, "more than 4095 column sources");
-      }
-      // Entries with many terms (pairs of shared parameters with many sources) are split into chunks of at
-      // most kCap terms: chunk 0 stores to the entry itself, every further chunk to a private
-      // partial cell that one thread adds to the entry afterwards, in a fixed order.
-      constexpr size_t kCap = 8; // = the records one trip of the kernel's loop consumes
-      struct Run {
-        int32_t dest; // >= 0: float offset in the tile region ; < 0: -(cell + 1) partial cell
-        size_t entry, first, count;
-      };
-      std::vector<Run> runs;
-      std::vector<int32_t> combDest, combFirst, combCount;
-      int32_t numCells = 0;
-      for (size_t e = 0; e < entries.size(); ++e) {
-        const size_t nt = entries[e].terms.size();
-        const size_t chunks = (nt + kCap - 1) / kCap;
-        for (size_t c = 0; c < chunks; ++c) {
-          const size_t first = c * kCap, count = std::min(kCap, nt - first);
-          runs.push_back(Run{c == 0 ? entries[e].dest : -(numCells + int32_t(c)), e, first, count});
-        }
-        if (chunks > 1) {
-          combDest.push_back(entries[e].dest);
-          combFirst.push_back(numCells);
-          combCount.push_back(int32_t(chunks - 1));
-          numCells += int32_t(chunks - 1);
-        }
-      }
-      // (chunk c >= 1 of an entry uses partial cell combFirst + c - 1)
-      // longest-processing-time-first assignment of runs to the threads of a workgroup (deterministic): 256 for the
-      // one-launch solve and the four-wave tree kernels, 1024 for the sixteen-wave treeNormalEquationsKernel
-      std::vector<size_t> order(runs.size());
-      for (size_t i = 0; i < order.size(); ++i) {
-        order[i] = i;
-      }
-      std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return runs[x].count > runs[y].count; });
-      auto deal = [&](int threads, std::vector<uint32_t>& inter) -> size_t {
-        const size_t nThreads = size_t(threads);
-        std::vector<std::vector<uint32_t>> recs(nThreads); // 4 words per record
-        std::vector<size_t> load(nThreads, 0);
-        for (size_t oi : order) {
-          const Run& rn = runs[oi];
-          int thread = 0;
-          for (int t = 1; t < threads; ++t) {
-            if (load[size_t(t)] < load[size_t(thread)]) {
-              thread = t;
-            }
-          }
-          const Entry& en = entries[rn.entry];
-          uint32_t destWord;
-          if (rn.dest >= 0) {
-            destWord = uint32_t(rn.dest);
-          } else {
-            destWord = (1u << 30) | uint32_t(-rn.dest - 1);
-          }
-          for (size_t i = 0; i < rn.count; ++i) {
-            const Term& tm = en.terms[rn.first + i];
-            uint32_t x = tm.deep | (tm.anc << 12) | (1u << 26);
-            if (i == 0) {
-              x |= 1u << 24;
-            }
-            if (i + 1 == rn.count) {
-              x |= 1u << 25;
-            }
-            uint32_t wbits;
-            std::memcpy(&wbits, &tm.w, 4);
-            recs[size_t(thread)].insert(recs[size_t(thread)].end(), {x, destWord, wbits, 0u});
-          }
-          load[size_t(thread)] += rn.count;
-        }
-        size_t rounds = 0;
-        for (const auto& r : recs) {
-          rounds = std::max(rounds, r.size() / 4);
-        }
-        rounds = (rounds + 7) & ~size_t(7); // the kernels consume 8 records per trip
-        inter.assign(std::max<size_t>(rounds, 8) * size_t(threads) * 4, 0u);
-        for (int t = 0; t < threads; ++t) {
-          for (size_t k = 0; k < recs[size_t(t)].size() / 4; ++k) {
-            for (int w = 0; w < 4; ++w) {
-              inter[(k * size_t(threads) + size_t(t)) * 4 + size_t(w)] = recs[size_t(t)][4 * k + size_t(w)];
-            }
-          }
-        }
-        return rounds;
-      };
-      std::vector<uint32_t> inter, inter16;
-      const size_t rounds = deal(256, inter), rounds16 = deal(1024, inter16);
-      if (numCells > 7 * rig->J) { // the kernels park the cells in a first-moment array: kC1 (= 7) floats per joint
-        return fail(MMX_ERR_UNSUPPORTED, "too many split H entries for the partial-cell scratch");
-      }
-      std::vector<int32_t> comb;
-      for (size_t i = 0; i < combDest.size(); ++i) {
-        comb.push_back(combDest[i]);
-        comb.push_back(combFirst[i]);
-        comb.push_back(combCount[i]);
-      }
-      MMX_HIP(upload(pb->dComb, comb));
-      fd.comb = pb->dComb.as<int32_t>();
-      fd.numComb = int32_t(combDest.size());
-      fd.numCells = numCells;
-      MMX_HIP(upload(pb->dTerms, inter));
-      fd.gTerms = pb->dTerms.as<uint4>();
-      fd.termRounds = int32_t(rounds);
-      MMX_HIP(upload(pb->dTerms16, inter16));
-      fd.gTerms16 = pb->dTerms16.as<uint4>();
-      fd.termRounds16 = int32_t(rounds16);
-    }
-    // limits per solve column, and the limits that share an off-diagonal entry of H
-    pb->limitPairs.clear();
-    {
-      std::vector<int32_t> colOf(size_t(rig->P), -1);
-      for (int32_t c = 0; c < fd.n; ++c) {
-        colOf[size_t(f.solveList[c])] = c;
-      }
-      std::vector<std::vector<int32_t>> per(size_t(std::max(fd.n, 1)));
-      std::map<int32_t, std::vector<int32_t>> pairs; // tile-region offset -> limits
-      std::map<int32_t, std::pair<int32_t, int32_t>> pairColumns;
-      for (size_t l = 0; l < pb->limits.size(); ++l) {
-        std::vector<int32_t> cols;
-        for (int32_t p : limitParameters(rig, pb->limits[l])) {
-          if (colOf[size_t(p)] >= 0) {
-            cols.push_back(colOf[size_t(p)]);
-          }
-        }
-        for (int32_t c : cols) {
-          per[size_t(c)].push_back(int32_t(l));
-        }
-        for (size_t x = 0; x < cols.size(); ++x) {
-          for (size_t y = x + 1; y < cols.size(); ++y) {
-            const int32_t row = std::max(cols[x], cols[y]), col = std::min(cols[x], cols[y]);
-            const int I = row >> 4, Jc = col >> 4, r = row & 15, c = col & 15;
-            const int32_t dest = (I * (I + 1) / 2 + Jc) * 256 + r * 16 + ((((c >> 2) ^ (r >> 2)) & 3) << 2) + (c & 3);
-            pairs[dest].push_back(int32_t(l));
-            pairColumns[dest] = {row, col};
-          }
-        }
-      }
-      std::vector<int32_t> limStart(1, 0), limOf, pairDest, pairStart(1, 0), pairLim;
-      for (int32_t c = 0; c < fd.n; ++c) {
-        limOf.insert(limOf.end(), per[size_t(c)].begin(), per[size_t(c)].end());
-        limStart.push_back(int32_t(limOf.size()));
-      }
-      std::vector<int32_t> pairCols;
-      for (const auto& kv : pairs) {
-        pairDest.push_back(kv.first);
-        pairCols.push_back(pairColumns[kv.first].first);
-        pairCols.push_back(pairColumns[kv.first].second);
-        pb->limitPairs.push_back(pairColumns[kv.first]);
-        pairLim.insert(pairLim.end(), kv.second.begin(), kv.second.end());
-        pairStart.push_back(int32_t(pairLim.size()));
-      }
-      MMX_HIP(upload(pb->dPairCols, pairCols));
-      fd.pairCols = pb->dPairCols.as<int32_t>();
-      MMX_HIP(upload(pb->dLimStart, limStart));
-      MMX_HIP(upload(pb->dLimOf, limOf));
-      MMX_HIP(upload(pb->dPairDest, pairDest));
-      MMX_HIP(upload(pb->dPairStart, pairStart));
-      MMX_HIP(upload(pb->dPairLim, pairLim));
-      fd.numLimits = int32_t(pb->limits.size());
-      fd.limStart = pb->dLimStart.as<int32_t>();
-      fd.limOf = pb->dLimOf.as<int32_t>();
-      fd.numPairDests = int32_t(pairDest.size());
-      fd.pairDest = pb->dPairDest.as<int32_t>();
-      fd.pairStart = pb->dPairStart.as<int32_t>();
-      fd.pairLim = pb->dPairLim.as<int32_t>();
-    }
-    pb->fdev.GT = pb->dev.G + int32_t(pb->ellipsoids.size());
-    pb->fdev.genRows = pb->fdev.GT > 0 ? pb->dev.rowsJoint - 3 * pb->U : 0;
-    const int32_t rcView = uploadSolveView(pb, slots);
-    if (rcView != MMX_OK) {
-      return rcView;
-    }
-  }
-  // Solve list of the explicit-Jacobian solver: an enabled parameter none of whose joint-parameter
-  // rows has a constraint below it has a zero column in J, so its step is 0 (H_pp = lambda, g_p = 0)
-  // and it can leave the dense system -- exactly, like the fused kernel's solve list.  Parameters
-  // touched by a limit or the model-parameter prior stay.  (Integer bookkeeping on the host.)
-  {
-    const size_t J = size_t(rig->J);
-    std::vector<uint8_t> anyBelow(J, 0), pointBelow(J, 0); // a constraint vector / a constraint POINT in the joint's subtree
-    auto mark = [&](int32_t joint, bool point) {
-      for (int32_t a = joint; a >= 0; a = rig->parent[size_t(a)]) {
-        anyBelow[size_t(a)] = 1;
-        if (point) {
-          pointBelow[size_t(a)] = 1;
-        }
-      }
-    };
-    for (int32_t c = 0; c < pb->Kp; ++c) {
-      mark(pb->posParent[size_t(c)], true);
-    }
-    for (int32_t c = 0; c < pb->Ko; ++c) {
-      mark(pb->oriParent[size_t(c)], false);
-    }
-    if (pb->instPos) {
-      for (int32_t j : pb->unionPos) {
-        mark(j, true);
-      }
-    }
-    if (pb->instOri) {
-      for (int32_t j : pb->unionOri) {
-        mark(j, false);
-      }
-    }
-    for (const auto& h : pb->blocks) {
-      const bool fixedAxis = h->type == MMX_JC_FIXED_AXIS_DIFF || h->type == MMX_JC_FIXED_AXIS_COS || h->type == MMX_JC_FIXED_AXIS_ANGLE;
-      for (int32_t j : h->parent) {
-        mark(j, !fixedAxis);
-      }
-      for (int32_t j : h->parentB) {
-        mark(j, true);
-      }
-    }
-    for (const mmx_ellipsoid_limit& e : pb->ellipsoids) {
-      mark(e.parent, true);
-    }
-    std::vector<uint8_t> keep(size_t(rig->P), pb->dev.hasModel ? 1 : 0);
-    for (const mmx_parameter_limit& lm : pb->limits) {
-      for (int32_t p : limitParameters(rig, lm)) {
-        keep[size_t(p)] = 1;
-      }
-    }
-    std::vector<int32_t> list;
-    for (int32_t p : t.eliminationList) {
-      bool nz = keep[size_t(p)] != 0;
-      for (int32_t e = t.colStart[size_t(p)]; !nz && e < t.colStart[size_t(p) + 1]; ++e) {
-        const mmx::ColumnSource& cs = t.colSources[size_t(e)];
-        nz = (cs.dof >= 3 && cs.dof < 6) ? anyBelow[size_t(cs.joint)] != 0 : pointBelow[size_t(cs.joint)] != 0;
-      }
-      if (nz) {
-        list.push_back(p);
-      }
-    }
-    if (list.empty()) {
-      list = t.eliminationList; // nothing to solve for: keep the plain system (all steps are zero)
-    }
-    MMX_HIP(upload(pb->dSolveListV1, list));
-    pb->solveN = int32_t(list.size());
-    pb->solveListV1 = list;
-    std::sort(list.begin(), list.end());
-    MMX_HIP(upload(pb->dSolveListF64, list));
-    pb->solveListF64 = list;
-    pb->f64ListUnitsPerChunk = 0;
-  }
-  // Tile structure of the wide solve's factor (HostTables::eliminationList): entry (row, col) of H can be non-zero when
-  // a source joint of the one column is an ancestor-or-self of a source joint of the other (their columns of J overlap
-  // only then) or when a limit couples the two parameters.  The further joint error functions / ellipsoid limits (rows
-  // over two joint chains) and systems the tree kernels do not take keep the dense structure.
-  {
-    const mmx::FusedTables& f = pb->fused;
-    const int32_t n = int32_t(f.solveList.size());
-    const bool dense = f.solveList != pb->solveListV1 || n > 512 || pb->fdev.GT > 0 || n == 0;
-    std::vector<uint8_t> related;
-    if (!dense) {
-      const size_t J = size_t(rig->J);
-      std::vector<uint8_t> reach(size_t(n) * J, 0); // joints in an ancestor relation with some source joint of column c
-      for (int32_t c = 0; c < n; ++c) {
-        uint8_t* rc = reach.data() + size_t(c) * J;
-        for (int32_t e = f.srcStart[size_t(c)]; e < f.srcStart[size_t(c) + 1]; ++e) {
-          const mmx::ColumnSource& cs = f.srcs[size_t(e)];
-          for (int32_t k = cs.tin; k < cs.tout; ++k) {
-            rc[size_t(f.dfsJoint[size_t(k)])] = 1;
-          }
-          for (int32_t a = cs.parent; a >= 0; a = rig->parent[size_t(a)]) {
-            rc[size_t(a)] = 1;
-          }
-        }
-      }
-      related.assign(size_t(n) * size_t(n), 0);
-      for (int32_t row = 0; row < n; ++row) {
-        for (int32_t col = 0; col < row; ++col) {
-          const uint8_t* rc = reach.data() + size_t(col) * J;
-          bool any = false;
-          for (int32_t e = f.srcStart[size_t(row)]; !any && e < f.srcStart[size_t(row) + 1]; ++e) {
-            any = rc[size_t(f.srcs[size_t(e)].joint)] != 0;
-          }
-          related[size_t(row) * size_t(n) + size_t(col)] = any ? 1 : 0;
-        }
-      }
-      for (const auto& rcPair : pb->limitPairs) {
-        related[size_t(rcPair.first) * size_t(n) + size_t(rcPair.second)] = 1;
-      }
-    }
-    pb->tileMasks = mmx::eliminationTileMasks(std::min(n, 512), related, dense);
-    std::vector<uint32_t> masks(96, 0u);
-    uint32_t base = 0;
-    for (int i = 0; i < 32; ++i) {
-      masks[size_t(i)] = pb->tileMasks.rowMask[i];
-      masks[size_t(32 + i)] = pb->tileMasks.colMask[i];
-      masks[size_t(64 + i)] = base; // first slot of block column i in the column-compact numbering
-      base += uint32_t(__builtin_popcount(pb->tileMasks.colMask[i]));
-    }
-    for (int k = 0; k < pb->tileMasks.NB && k < 32; ++k) { // [96 + slot]: the tile in that slot, I | k << 8 (the resident kernels' load lists)
-      for (int I = k; I < 32; ++I) {
-        if (pb->tileMasks.colMask[k] >> I & 1u) {
-          masks.push_back(uint32_t(I) | uint32_t(k) << 8);
-        }
-      }
-    }
-    // ... and behind the slots the level schedule of the factorisation (TileMasks::levelSteps; [96 + tiles]: numSteps, then
-    // four words per step)
-    for (int32_t w : pb->tileMasks.levelSteps) {
-      masks.push_back(uint32_t(w));
-    }
-    MMX_HIP(upload(pb->dTileMasks, masks));
-    MMX_HIP(upload(pb->dTileList, pb->tileMasks.tiles));
-    pb->fdev.tileList = pb->dTileList.as<int32_t>();
-    pb->fdev.numTiles = int32_t(pb->tileMasks.tiles.size());
-  }
-
-  return MMX_OK;
+  d.numJacRecs = int32_t(cp.recs.size());
+  d.numMultiCols = int32_t(cp.multi.size());
+  d.numZeroCols = int32_t(cp.zero.size());
+  mmx::FusedDev& fd = pb->fdev;
+  fd.U = pb->U;
+  fd.Kp = pb->Kp;
+  fd.n = n;
+  fd.nsrc = int32_t(st.slots.size());
+  fd.slotBase = st.slotBase;
+  fd.nnz = rig->ptOuter.back();
+  fd.subSize = pb->dSubSize.as<int32_t>();
+  fd.dfsJoint = pb->dDfsJoint.as<int32_t>();
+  fd.loadedPos = pb->dLoadedPos.as<int32_t>();
+  fd.numLoaded = int32_t(st.loadedPos.size());
+  fd.unitJoint = pb->dUnitJoint.as<int32_t>();
+  fd.posUnitStart = pb->dPosUnitStart.as<int32_t>();
+  fd.posUnits = pb->dPosUnits.as<int32_t>();
+  fd.solveList = pb->dSolveList.as<int32_t>();
+  fd.srcStart = pb->dSrcStart.as<int32_t>();
+  fd.srcs = pb->dSrcs.as<mmx::ColumnSourceDev>();
+  fd.comb = pb->dComb.as<int32_t>();
+  fd.numComb = int32_t(runs.comb.size() / 3);
+  fd.numCells = runs.numCells;
+  fd.gTerms = pb->dTerms.as<uint4>();
+  fd.termRounds = int32_t(rounds);
+  fd.gTerms16 = pb->dTerms16.as<uint4>();
+  fd.termRounds16 = int32_t(rounds16);
+  fd.pairCols = pb->dPairCols.as<int32_t>();
+  fd.numLimits = int32_t(pb->limits.size());
+  fd.limStart = pb->dLimStart.as<int32_t>();
+  fd.limOf = pb->dLimOf.as<int32_t>();
+  fd.numPairDests = int32_t(lt.pairDest.size());
+  fd.pairDest = pb->dPairDest.as<int32_t>();
+  fd.pairStart = pb->dPairStart.as<int32_t>();
+  fd.pairLim = pb->dPairLim.as<int32_t>();
+  fd.GT = G + NE;
+  fd.genRows = fd.GT > 0 ? d.rowsJoint - 3 * pb->U : 0;
+  fd.tileList = pb->dTileList.as<int32_t>();
+  fd.numTiles = int32_t(pb->tileMasks.tiles.size());
+  pb->viewBuilt = false;
+  return wantView ? uploadSolveView(pb, lv) : MMX_OK;
 }
 
 // What the one-launch solve, its mixed-precision instantiation, the wave route and the tree kernels are launched with: the
@@ -1559,7 +907,7 @@ int32_t mmx_rig_create(const mmx_rig_desc* d, int32_t device, mmx_rig** out) {
   UP(r->dLevelStart, r->topo.levelStart);
   // two-slot ELL copy of the parameter transform, the packed level/parent table of the J-assembly kernel and the records of
   // the non-empty transform rows (deriveRigTables)
-  const RigDerived rd = deriveRigTables(r->J, r->P, r->parent, r->ptOuter, r->ptInner, r->ptValue, int32_t(r->topo.levelStart.size()) - 1);
+  const mmx::RigDerived rd = mmx::deriveRigTables(r->J, r->P, r->parent, r->ptOuter, r->ptInner, r->ptValue, int32_t(r->topo.levelStart.size()) - 1);
   const bool ellOk = rd.ellOk;
   const std::vector<int32_t>& rowRec = rd.rowRec;
   if (ellOk) {
@@ -1971,6 +1319,7 @@ int32_t mmx_problem_set_constraints(mmx_problem* pb, const mmx_constraint_data* 
   if ((c->model_target == nullptr) != (c->model_weights == nullptr)) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "model_target and model_weights must be given together");
   }
+  const mmx_rig_desc rigDesc = pb->rig->desc();
   for (int32_t l = 0; l < c->num_limits; ++l) {
     const mmx_parameter_limit& lm = c->limits[l];
     const bool model = lm.type == MMX_LIMIT_MINMAX || lm.type == MMX_LIMIT_LINEAR || lm.type == MMX_LIMIT_HALFPLANE;
@@ -1990,7 +1339,7 @@ int32_t mmx_problem_set_constraints(mmx_problem* pb, const mmx_constraint_data* 
     if (lm.index0 < 0 || lm.index0 >= bound || (two && (lm.index1 < 0 || lm.index1 >= bound))) {
       return fail(MMX_ERR_INVALID_ARGUMENT, "limit " + std::to_string(l) + ": parameter index out of range"); // MT_CHECK :574-575,:611-612
     }
-    if (limitParameters(pb->rig, lm).size() > 4) {
+    if (mmx::limitParameters(&rigDesc, lm).size() > 4) {
       return fail(MMX_ERR_UNSUPPORTED, "limit " + std::to_string(l) + ": more than four model parameters drive the limited joint parameters");
     }
   }

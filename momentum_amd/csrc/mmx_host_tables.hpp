@@ -5,11 +5,13 @@
 // ParameterTransformT::computeActiveJointParams (momentum/character/parameter_transform.cpp:97-107)
 // and a column-wise (CSC) view of the enabled part of the parameter transform, which is what lets
 // the kernels GATHER a Jacobian column instead of scattering like the reference's ancestor walk
-// (momentum/character_solver/joint_error_function-inl.h:228-294).
+// (momentum/character_solver/joint_error_function-inl.h:228-294).  The second half of the file builds every table a problem
+// uploads (slots, term records, limit tables, tile structure, the live-joint view): tests/cpp/test_problem_tables.cpp.
 #pragma once
 
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mmx.h"
@@ -162,5 +164,202 @@ int32_t validateRigDesc(const mmx_rig_desc* d, std::string& err);
 
 // Builds all tables.  `enabled` may be null (= all parameters enabled).
 int32_t buildHostTables(const mmx_rig_desc* d, const uint8_t* enabled, HostTables& out, std::string& err);
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Problem tables.  Everything below is what mmx_capi.hip uploads for a problem (uploadProblemTables, uploadSolveView): the
+// upload path gathers a ProblemTopology from its handle, calls these builders and copies the vectors to the device.  One
+// function per table family, each callable on its own.  They are internal to the library: the exported interface stays the C ABI.
+#pragma GCC visibility push(hidden)
+
+// model parameters that can carry a non-zero Jacobian entry of a limit row
+std::vector<int32_t> limitParameters(const mmx_rig_desc* d, const mmx_parameter_limit& lm);
+
+// Tables derived from a rig's host arrays: the two-slot ELL copy of the parameter transform (one 16-byte record per
+// joint-parameter row), the packed parent / jump-target table, the records of the non-empty transform rows
+// (RigDev::ptRowRec) and the pointer-jumping round count.  mmx_rig_create builds them for the rig, the live-joint view of a
+// problem for its joints.
+struct RigDerived {
+  std::vector<int32_t> ell, jumpParent, rowRec;
+  bool ellOk = true;
+  int32_t jumpRounds = 0;
+};
+RigDerived deriveRigTables(
+    int32_t J, int32_t P, const std::vector<int32_t>& parent, const std::vector<int32_t>& ptOuter, const std::vector<int32_t>& ptInner,
+    const std::vector<float>& ptValue, int32_t numLevels);
+
+// What a problem references, as plain data.
+struct ProblemTopology {
+  int32_t Kp = 0, Ko = 0;
+  std::vector<int32_t> posParent, oriParent; // [Kp], [Ko]
+  bool instPos = false, instOri = false; // per-instance constraint parents: unionPos / unionOri apply
+  std::vector<int32_t> unionPos, unionOri; // joints that carry a position / orientation constraint in some element
+  struct Block {
+    int32_t type = 0; // MMX_JC_*
+    std::vector<int32_t> parent;
+    std::vector<int32_t> parentB; // MMX_JC_JOINT_TO_JOINT_DISTANCE: the second joint of every constraint, else empty
+  };
+  std::vector<Block> blocks;
+  std::vector<mmx_ellipsoid_limit> ellipsoids;
+  std::vector<mmx_parameter_limit> limits;
+  bool hasModel = false; // the model-parameter block is present
+  int32_t U() const {
+    return Kp + 3 * Ko;
+  }
+};
+
+// The joints the problem references (LiveJoints): constraint parents, the joints of the further blocks and of ellipsoid
+// limits, the joints of joint-parameter limits.
+std::vector<int32_t> referencedJoints(const ProblemTopology& p);
+
+// Float offset of entry (row, col), row >= col, in the tile region of H: 16 x 16 tiles in I (I + 1) / 2 + J order, a tile's
+// rows 16 floats apart with their four-float groups swizzled by the row (tileAddr() of the kernels).
+inline int32_t tileAddress(int32_t row, int32_t col) {
+  const int32_t I = row >> 4, Jc = col >> 4, r = row & 15, c = col & 15;
+  return (I * (I + 1) / 2 + Jc) * 256 + r * 16 + ((((c >> 2) ^ (r >> 2)) & 3) << 2) + (c & 3);
+}
+
+// The tables indexed by joint: units, the flattened constraints of the further blocks ([G], then [G] second joints: the B
+// joint of a pair constraint, -1 for every other type) and the joint words of the ellipsoid records.  `compactOf` renumbers
+// the joints (null: as they are) and tin / tout are indexed by the renumbered joint, so the full tables and the live-joint
+// view are the same code.
+struct JointTables {
+  std::vector<int32_t> unitJoint, unitTin; // [max(U, 1)]
+  std::vector<int32_t> genJoint, genTin; // [2 G]
+  std::vector<int32_t> genBlock; // [G]
+  std::vector<int32_t> ellParent, ellEllipsoidParent; // [NE]
+  std::vector<int32_t> ellTinParent; // [NE] tin[parent]
+  std::vector<int32_t> ellTinStop; // [NE] tin[ellipsoidParent] when that joint is an ancestor-or-self of `parent`, else -1
+};
+JointTables buildJointTables(const ProblemTopology& p, const int32_t* compactOf, const std::vector<int32_t>& tin, const std::vector<int32_t>& tout);
+
+// What buildFusedTables is fed beside the constraint parents: the parameters a limit or (all of them) the model-parameter
+// block touches stay in the solve list; joints that carry a further joint error function or an ellipsoid limit count like
+// constrained joints for the structure -- point-like ones (projection, distance and BOTH joints of a pair among them) see
+// every dof above them, fixed-axis ones rotations only.
+struct StructureLists {
+  std::vector<uint8_t> force; // [P]
+  std::vector<int32_t> structPos, structOri;
+};
+StructureLists buildStructureLists(const mmx_rig_desc* d, const ProblemTopology& p);
+// ... and buildFusedTables called with them
+int32_t buildProblemFusedTables(
+    const mmx_rig_desc* d, const HostTables& t, const ProblemTopology& p, const StructureLists& s, FusedTables& out, std::string& err);
+
+// Column program of the J-assembly kernel, specialised to the problem: a column whose sources have no constraint vector
+// below them (or that is disabled) is structurally zero -- it moves to the zero list, which the kernel writes BEFORE forward
+// kinematics; the rest as in buildHostTables.
+struct ColumnProgram {
+  std::vector<JacRec> recs; // sorted by (joint, dof), padded to a multiple of 4 with copies of the last record
+  std::vector<int32_t> multi, zero;
+};
+ColumnProgram buildColumnProgram(const HostTables& t, const FusedTables& f);
+
+// Source SLOTS of the fused kernel.  Column c of the compacted system keeps its first source in slot c (the "primary"
+// source: with it alone the slot index IS the column index, so the 16 x 16 tiles of H = J^T J come straight out of
+// matrix-core products of the per-slot moment contractions); slots n .. slotBase-1 pad the last block (weight 0); the further
+// sources of multi-source columns (shared parameters) follow from slot slotBase on, in column order: extras of column c =
+// slots slotBase + xStart[c] .. slotBase + xStart[c+1] - 1.  slotBase = 16 * slotBlocks; the caller picks the block count
+// (the kernels' instantiations).  The slot count is a multiple of 4.
+struct SlotTables {
+  int32_t slotBase = 0;
+  std::vector<int32_t> loadedPos; // DFS positions that carry a unit, ascending
+  std::vector<ColumnSource> slots;
+  std::vector<int32_t> xStart; // [slotBase + 1]
+  std::vector<int32_t> slotOf; // [srcs] source e of FusedTables::srcs -> its slot
+};
+SlotTables buildSlotTables(const FusedTables& f, int32_t slotBlocks);
+
+// Structural term records of H for the pairs the matrix-core pass does not cover: entry (row, col), row >= col, receives one
+// term per pair (source a of row, source c of col) whose joints are in an ancestor relation AND of which at least one is an
+// extra source; the deeper source supplies the moment contractions, the other one alpha / B (weights are folded into the
+// per-slot tables, a record's weight word stays 1).  Entries with many terms are split into runs of at most kTermCap terms:
+// run 0 stores to the entry itself, every further run to a private partial cell that one thread adds to the entry
+// afterwards, in a fixed order (the combine list).
+constexpr size_t kTermCap = 8; // = the records one trip of the kernels' loop consumes
+struct TermRuns {
+  struct Term {
+    uint32_t deep, anc; // slots
+  };
+  struct Entry {
+    int32_t dest; // tileAddress(row, col)
+    std::vector<Term> terms;
+  };
+  struct Run {
+    int32_t dest; // >= 0: float offset in the tile region ; < 0: -(cell + 1) partial cell
+    size_t entry, first, count;
+  };
+  std::vector<Entry> entries;
+  std::vector<Run> runs;
+  std::vector<int32_t> comb; // three words per split entry: its dest, its first partial cell, its cells
+  int32_t numCells = 0;
+};
+// MMX_ERR_UNSUPPORTED "more than 4095 column sources" (a record packs a slot into 12 bits) and "too many split H entries for
+// the partial-cell scratch" (the kernels park the cells in a first-moment array: 7 floats per joint)
+int32_t buildTermRuns(const FusedTables& f, const SlotTables& s, int32_t J, TermRuns& out, std::string& err);
+// Longest-processing-time-first assignment of the runs to `threads` threads (deterministic): 256 for the one-launch solve and
+// the four-wave tree kernels, 1024 for the sixteen-wave treeNormalEquationsKernel.  A record is four words: deep | anc << 12
+// | first-of-run << 24 | last-of-run << 25 | 1 << 26, the dest word (bit 30: a partial cell), the weight's bits, 0.  A
+// thread's records are stored interleaved (record k of thread t at [k * threads + t]) so that a wave reads them coalesced.
+// Returns the rounds, a multiple of 8 (`inter` holds at least 8).
+size_t dealTermRuns(const TermRuns& r, int threads, std::vector<uint32_t>& inter);
+
+// Limits per solve column (limStart / limOf), and the limits that share an off-diagonal entry of H: per tile-region offset
+// in ascending order (pairDest) its limits (pairStart / pairLim) and its (row, col) solve columns (pairCols, limitPairs).
+struct LimitTables {
+  std::vector<int32_t> limStart, limOf, pairDest, pairStart, pairLim, pairCols;
+  std::vector<std::pair<int32_t, int32_t>> limitPairs;
+};
+LimitTables buildLimitTables(const mmx_rig_desc* d, const std::vector<mmx_parameter_limit>& limits, const std::vector<int32_t>& solveList);
+
+// Solve list of the explicit-Jacobian solver: an enabled parameter none of whose joint-parameter rows has a constraint
+// below it has a zero column in J, so its step is 0 (H_pp = lambda, g_p = 0) and it can leave the dense system -- exactly,
+// like the fused kernel's solve list.  Forced parameters (StructureLists::force) stay.  In elimination order; `sorted` is the
+// same set in index order (the double solve follows the reference's column order).  With nothing to solve for, the plain
+// system is kept (all steps are zero).
+struct ExplicitSolveLists {
+  std::vector<int32_t> list, sorted;
+};
+ExplicitSolveLists buildExplicitSolveLists(const mmx_rig_desc* d, const HostTables& t, const ProblemTopology& p, const std::vector<uint8_t>& force);
+
+// Tile structure of the wide solve's factor: entry (row, col) of H can be non-zero when a source joint of the one column is
+// an ancestor-or-self of a source joint of the other (their columns of J overlap only then) or when a limit couples the two
+// parameters.  The further joint error functions / ellipsoid limits (GT of them: rows over two joint chains) and systems the
+// tree kernels do not take keep the dense structure.
+bool tileStructureDense(const FusedTables& f, const std::vector<int32_t>& explicitList, int32_t GT);
+std::vector<uint8_t> buildRelatedness(const mmx_rig_desc* d, const FusedTables& f, const std::vector<std::pair<int32_t, int32_t>>& limitPairs);
+// The device array of a TileMasks: [32] row masks, [32] column masks, [32] first slot of block column i in the column-compact
+// numbering; from [96] the tile in every slot, I | k << 8 (the resident kernels' load lists), then the level schedule.
+std::vector<uint32_t> packTileMasks(const TileMasks& m);
+
+// The live-joint view's tables: everything the solve kernels index by joint or by DFS position, REMAPPED from the full
+// tables (solve list, elimination order, term records and tile structure stay as they are).
+struct CompactRig { // the rig over the live joints
+  std::vector<int32_t> parent, ptOuter, ptInner;
+  std::vector<float> preRot, offset, ptValue, ptOffsets;
+};
+CompactRig buildCompactRig(const mmx_rig_desc* d, const LiveJoints& lj);
+// Levels and the DFS interval of every live joint in the compact numbering: a live joint's ancestors are live, so its level
+// is the full rig's, and the live positions keep their order (rank among the live positions).
+struct CompactOrder {
+  std::vector<int32_t> levelStart, levelOrder; // [numLevels + 1], [numLive]
+  std::vector<int32_t> tin, tout; // [numLive]
+  std::vector<int32_t> posOf; // [J] full DFS position -> live position, -1 for a dead one
+};
+CompactOrder buildCompactOrder(const HostTables& t, const FusedTables& f, const LiveJoints& lj);
+struct LiveView {
+  CompactRig rig;
+  CompactOrder order;
+  RigDerived derived;
+  JointTables joints;
+  std::vector<mmx_parameter_limit> limits; // joint-parameter rows renumbered
+  std::vector<int32_t> subSize, dfsJoint; // [numLive] by live DFS position
+  std::vector<int32_t> loadedPos;
+  std::vector<int32_t> posUnitStart; // [numLive + 1]; indexes the FULL posUnits (a dead position carries no unit)
+  std::vector<ColumnSource> slots; // pad and dead slots: weight as it was, empty interval
+};
+LiveView buildLiveView(
+    const mmx_rig_desc* d, const HostTables& t, const FusedTables& f, const ProblemTopology& p, const LiveJoints& lj,
+    const std::vector<ColumnSource>& slots);
+#pragma GCC visibility pop
 
 } // namespace mmx
