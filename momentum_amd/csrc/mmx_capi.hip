@@ -17,11 +17,13 @@
 #include <new>
 #include <map>
 #include <memory>
+#include <numeric>
 #include <string>
 #include <vector>
 
 #include "mmx_host_tables.hpp"
 #include "mmx_kernels.hpp"
+#include "mmx_solve_plan.hpp"
 
 namespace {
 
@@ -40,6 +42,15 @@ int32_t fail(int32_t code, const std::string& msg) {
           e_ == hipErrorOutOfMemory ? MMX_ERR_OUT_OF_MEMORY : MMX_ERR_DEVICE,                     \
           std::string(#call) + ": " + hipGetErrorString(e_));                                     \
     }                                                                                             \
+  } while (0)
+
+// ... and the same for a step that answers with a status code of its own
+#define MMX_TRY(call)        \
+  do {                       \
+    int32_t rc_ = (call);    \
+    if (rc_ != MMX_OK) {     \
+      return rc_;            \
+    }                        \
   } while (0)
 
 // ---- profiling zones: roctx ranges around the ABI entry points and the phases of the explicit-Jacobian
@@ -233,7 +244,6 @@ struct mmx_problem {
   DevBuf sDiagErr0; // [B] ... and the first iteration's error (mmx::StepParams::diagErr0)
   bool diagValid = false;
   DevBuf sThetaAuto, sAutoMap, sAutoCount; // MMX_PRECISION_AUTO: initial parameters, the elements to escalate, their number
-  bool autoAbort = false; // ... its single-precision pass may leave a marked element after the first factorisation
   mmx_tuning tuning{}; // mmx_problem_set_tuning
   int32_t lastRoute = MMX_ROUTE_AUTO;
   // The live-joint view (solveView below): the rig and the joint-indexed tables over the joints the solve can depend on,
@@ -1572,10 +1582,7 @@ int32_t mmx_eval_jacobian(
     int32_t layout,
     void* stream) {
   MMX_ZONE("mmx_eval_jacobian (initializeJacobianComputation + computeJacobianBlock)");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, true));
   if (theta_dev == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "theta is null");
   }
@@ -1605,10 +1612,7 @@ int32_t mmx_eval_jacobian_timed(
     int32_t layout,
     void* stream,
     float* kernel_ms) {
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, true));
   if (theta_dev == nullptr || jac_dev == nullptr || kernel_ms == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "theta / jac / kernel_ms is null");
   }
@@ -1638,10 +1642,7 @@ int32_t mmx_eval_jacobian_timed(
 }
 
 int32_t mmx_debug_store_pattern(mmx_problem* pb, float* jac_dev, void* stream, float* kernel_ms) {
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, true));
   if (jac_dev == nullptr || kernel_ms == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "jac / kernel_ms is null");
   }
@@ -1671,10 +1672,7 @@ int32_t mmx_debug_store_pattern(mmx_problem* pb, float* jac_dev, void* stream, f
 
 int32_t mmx_eval_skeleton_state(mmx_problem* pb, const float* theta_dev, float* state_dev, void* stream) {
   MMX_ZONE("mmx_eval_skeleton_state (SkeletonState::set)");
-  int32_t rc = checkProblem(pb, false);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, false));
   if (theta_dev == nullptr || state_dev == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "theta / state is null");
   }
@@ -1706,10 +1704,7 @@ int32_t mmx_eval_normal_equations(
     double* err_dev,
     void* stream) {
   MMX_ZONE("mmx_eval_normal_equations (Get JtJ and JtR)");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, true));
   if (theta_dev == nullptr || jtj_dev == nullptr || jtr_dev == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "theta / jtj / jtr is null");
   }
@@ -1718,10 +1713,7 @@ int32_t mmx_eval_normal_equations(
   }
   MMX_HIP(hipSetDevice(pb->rig->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  rc = ensureStepScratch(pb);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(ensureStepScratch(pb));
   MMX_HIP(mmx::launchFkJacobian(
       pb->rigDev, pb->dev, theta_dev, pb->sJac.as<float>(), pb->sRes.as<float>(), err_dev, nullptr, nullptr, s));
   MMX_HIP(mmx::launchNormalEquations(
@@ -1731,10 +1723,7 @@ int32_t mmx_eval_normal_equations(
 
 int32_t mmx_debug_tree_normal_equations(mmx_problem* pb, const float* theta_dev, float* jtj_dev, float* jtr_dev, void* stream) {
   MMX_ZONE("mmx_debug_tree_normal_equations");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, true));
   if (theta_dev == nullptr || jtj_dev == nullptr || jtr_dev == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "theta / jtj / jtr is null");
   }
@@ -1749,65 +1738,8 @@ int32_t mmx_debug_tree_normal_equations(mmx_problem* pb, const float* theta_dev,
   return MMX_OK;
 }
 
-static int32_t solveImpl(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    float* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    float* parameter_history,
-    double* step_history,
-    void* stream);
-
-int32_t mmx_solve(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    float* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    void* stream) {
-  return solveImpl(pb, o, theta_dev, final_error, iterations, status, error_history, nullptr, nullptr, stream);
-}
-
-int32_t mmx_solve_with_history(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    float* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    float* parameter_history,
-    void* stream) {
-  return solveImpl(pb, o, theta_dev, final_error, iterations, status, error_history, parameter_history, nullptr, stream);
-}
-
-int32_t mmx_solve_with_step_history(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    float* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    float* parameter_history,
-    double* step_history,
-    void* stream) {
-  if (step_history != nullptr && o != nullptr && o->step_rule != MMX_STEP_LM_SCHEDULE) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_solve_with_step_history: step_history is the LM schedule's (MMX_STEP_LM_SCHEDULE)");
-  }
-  return solveImpl(pb, o, theta_dev, final_error, iterations, status, error_history, parameter_history, step_history, stream);
-}
-
 int32_t mmx_problem_solve_diagnostics(mmx_problem* pb, float* diag_dev, void* stream) {
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, true));
   if (diag_dev == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "diag_dev is null");
   }
@@ -1819,669 +1751,250 @@ int32_t mmx_problem_solve_diagnostics(mmx_problem* pb, float* diag_dev, void* st
   return MMX_OK;
 }
 
-static int32_t solveF32Impl(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    float* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    float* parameter_history,
-    double* step_history,
-    void* stream);
-static int32_t solveF64Impl(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    double* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    double* step_history,
-    const mmx::F64Select& select,
-    void* stream);
-static int32_t preflightF64(mmx_problem* pb);
+// ---------------------------------------------------------------------------------------------------------------------
+// The solve dispatch.  An entry point checks its handle and pointers, gathers the facts the decision reads (solveFacts), asks
+// mmx_solve_plan.cpp for the plan and either fails with the plan's refusal -- before theta, an output, lastRoute or diagValid
+// is touched -- or runs the plan's stages: one executor per route and precision below, on the shared set-up blocks.
+extern "C++" {
+namespace {
 
-// MMX_PRECISION_MIXED (and MMX_PRECISION_AUTO's second pass): does the mixed-precision instantiation of the one-launch solve
-// take this problem with these options?  Position / orientation constraints and the parameter-space rows (limits on model / joint
-// parameters, the model-parameter prior); not the further joint error functions / ellipsoid limits, not the trust region, the route
-// not pinned away from the one-launch solve.
-static bool mixedUsable(const mmx_problem* pb, const mmx_gn_options* o) {
-  if (o == nullptr || pb == nullptr || pb->rig == nullptr) {
-    return false;
-  }
-  const int32_t route = pb->tuning.route;
-  return (route == MMX_ROUTE_AUTO || route == MMX_ROUTE_FUSED) && o->step_rule != MMX_STEP_TRUST_REGION && pb->fdev.GT == 0 &&
-      pb->U > 0 && pb->fdev.n > 0 && fusedUsable(pb) &&
-      mmx::fusedMixedUsable(pb->rig->J, pb->rig->P, pb->U, pb->fdev.nsrc, pb->fdev.n, pb->fdev.numCells);
-}
+static_assert(mmx::kPlanMaxSolved == mmx::kMaxSolved, "the solve plan's bound is the kernels'");
 
-// MMX_ROUTE_WAVE (mmx_wave.hip, scope table in include/mmx.h): null when the one-wavefront-per-instance solve takes this
-// problem with these options, else the condition it fails (the pinned route then answers MMX_ERR_UNSUPPORTED with it)
-static const char* waveRefusal(const mmx_problem* pb, const mmx_gn_options* o, bool frames = false) {
+// the optional outputs of a solve, as the caller passed them (null: not wanted)
+struct SolveOutputs {
+  double* finalError;
+  int32_t* iterations;
+  int32_t* status;
+  double* errorHistory;
+  float* parameterHistory;
+  double* stepHistory;
+};
+
+// What the plan reads, gathered in one place.  The sizing functions stay with their kernels.  The budgets of kernels the call
+// cannot reach are left at their defaults: the wave route's unless it is pinned or asked for (mmx_solve_frames), the mixed and
+// double kernels' under MMX_PRECISION_F32 (mmx_solve_f64 passes another precision).
+mmx::SolveFacts solveFacts(const mmx_problem* pb, const SolveOutputs& out, int32_t precision, bool wave) {
   const mmx::ProblemDev& d = pb->dev;
-  if (pb->rig->J > MMX_WAVE_MAX_JOINTS) {
-    return "MMX_ROUTE_WAVE: more than MMX_WAVE_MAX_JOINTS (64) joints";
+  const int J = pb->rig->J, P = pb->rig->P, U = pb->U, n = pb->fdev.n;
+  mmx::SolveFacts f;
+  f.route = pb->tuning.route;
+  f.refineSteps = refineSteps(pb);
+  f.fusedUsable = fusedUsable(pb);
+  f.treeUsable = treeNormalEquationsUsable(pb);
+  f.fusedBlocks = mmx::fusedBlocksFor(n);
+  f.choleskyStepLdsBytes = mmx::choleskyStepLdsBytes(pb->solveN, d.M);
+  if (wave) {
+    f.waveLdsBytes = mmx::waveLdsBytes(J, P, U, n, false);
+    f.waveFramesLdsBytes = mmx::waveLdsBytes(J, P, U, n, true);
   }
-  if (pb->fdev.n > MMX_WAVE_MAX_SOLVED) {
-    return "MMX_ROUTE_WAVE: more than MMX_WAVE_MAX_SOLVED (32) solved parameters";
+  if (precision != MMX_PRECISION_F32) {
+    const int genRowsF64 = d.rowsJoint - 3 * U;
+    f.fusedMixedUsable = mmx::fusedMixedUsable(J, P, U, pb->fdev.nsrc, n, pb->fdev.numCells);
+    f.f64Resident = mmx::solveF64IsResident(J, P, U, pb->solveN, d.G + d.NE, genRowsF64);
+    f.f64LdsBytes = mmx::solveF64LdsBytes(J, P, U, pb->solveN, d.G + d.NE, genRowsF64);
   }
-  if (pb->fdev.n <= 0 || pb->U <= 0) {
-    return "MMX_ROUTE_WAVE: no solved parameter, or no position / orientation constraint";
-  }
-  if (pb->U > MMX_WAVE_MAX_UNITS) {
-    return "MMX_ROUTE_WAVE: more than MMX_WAVE_MAX_UNITS (192) constraint vectors (positions + 3 x orientations)";
-  }
-  if (d.lossPos.type != 0 || d.lossOri.type != 0) {
-    return "MMX_ROUTE_WAVE: robust losses are outside the route (L2 only)";
-  }
-  if (d.numBlocks > 0 || d.G > 0 || pb->fdev.GT > 0) {
-    return "MMX_ROUTE_WAVE: further joint-constraint blocks are outside the route";
-  }
-  if (d.NE > 0) {
-    return "MMX_ROUTE_WAVE: ellipsoid limits are outside the route";
-  }
-  if (d.NL > 0) {
-    return "MMX_ROUTE_WAVE: parameter limits are outside the route";
-  }
-  if (d.hasModel != 0 || d.M > d.rowsJoint) {
-    return "MMX_ROUTE_WAVE: the model-parameter prior is outside the route";
-  }
-  if (d.instPosParent != nullptr || d.instOriParent != nullptr) {
-    return "MMX_ROUTE_WAVE: per-instance constraint parents are outside the route";
-  }
-  if (o->step_rule != MMX_STEP_GN_FIXED_LAMBDA) {
-    return "MMX_ROUTE_WAVE: only MMX_STEP_GN_FIXED_LAMBDA (not the LM schedule, not the trust region)";
-  }
-  if (mmx::waveLdsBytes(pb->rig->J, pb->rig->P, pb->U, pb->fdev.n, frames) > 160 * 1024) { // (frames: one more parameter vector per wave)
-    return "MMX_ROUTE_WAVE: the parameter vector does not fit a wave's share of LDS";
-  }
-  return nullptr;
+  f.J = J;
+  f.n = n;
+  f.solveN = pb->solveN;
+  f.U = U;
+  f.M = d.M;
+  f.rowsJoint = d.rowsJoint;
+  f.GT = pb->fdev.GT;
+  f.G = d.G;
+  f.NE = d.NE;
+  f.NL = d.NL;
+  f.numBlocks = d.numBlocks;
+  f.hasModel = d.hasModel;
+  f.lossPosType = d.lossPos.type;
+  f.lossOriType = d.lossOri.type;
+  f.instanceParents = d.instPosParent != nullptr || d.instOriParent != nullptr;
+  f.parameterHistory = out.parameterHistory != nullptr;
+  f.stepHistory = out.stepHistory != nullptr;
+  return f;
 }
 
-static int32_t solveMixedImpl(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    float* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    float* parameter_history,
-    double* step_history,
-    const mmx::MixSelect& sel,
-    void* stream) {
-  MMX_ZONE("mmx_solve, mixed precision (SolverT<double>::solve around a single-precision factor)");
-  if (o->max_iterations < 0 || o->min_iterations < 0) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "iteration counts must be >= 0");
-  }
-  if (o->step_rule != MMX_STEP_GN_FIXED_LAMBDA && o->step_rule != MMX_STEP_LM_SCHEDULE) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "unknown step_rule");
-  }
-  if (o->do_line_search != MMX_LINE_SEARCH_NONE && o->do_line_search != MMX_LINE_SEARCH_GAUSS_NEWTON && o->do_line_search != MMX_LINE_SEARCH_DIRECTIONAL) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "unknown do_line_search rule");
-  }
-  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool escalation = sel.map != nullptr; // (the single-precision pass's outputs stay for the other elements)
-  pb->lastRoute = MMX_ROUTE_FUSED;
+// ---- the set-up blocks every executor shares
+
+// The three default output buffers, and the solve state with the caller's pointers or the defaults
+int32_t bindOutputs(mmx_problem* pb, const SolveOutputs& out, mmx::SolveStateDev& st) {
+  const size_t B = size_t(pb->B);
   MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
   MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
   MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
-  mmx::SolveStateDev fst{};
-  fst.iterations = iterations != nullptr ? iterations : pb->sIters.as<int32_t>();
-  fst.status = status != nullptr ? status : pb->sStatus.as<int32_t>();
-  fst.finalError = final_error != nullptr ? final_error : pb->sFinalErr.as<double>();
-  fst.errorHistory = error_history;
-  fst.paramHistory = parameter_history;
-  fst.stepHistory = step_history;
-  if (!escalation) {
-    MMX_HIP(pb->sDiag.ensure(B * 4 * sizeof(float)));
-    fst.diag = pb->sDiag.as<float>();
-    pb->diagValid = true;
-    if (step_history != nullptr && o->max_iterations > 0) {
-      MMX_HIP(mmx::zeroAsync(step_history, B * size_t(o->max_iterations) * 2 * sizeof(double), s));
-    }
-    if (error_history != nullptr && o->max_iterations > 0) {
-      MMX_HIP(mmx::zeroAsync(error_history, B * size_t(o->max_iterations) * sizeof(double), s));
-    }
-    if (parameter_history != nullptr && o->max_iterations > 0) {
-      MMX_HIP(mmx::zeroAsync(parameter_history, B * size_t(o->max_iterations) * P * sizeof(float), s));
-    }
+  st = mmx::SolveStateDev{};
+  st.iterations = out.iterations != nullptr ? out.iterations : pb->sIters.as<int32_t>();
+  st.status = out.status != nullptr ? out.status : pb->sStatus.as<int32_t>();
+  st.finalError = out.finalError != nullptr ? out.finalError : pb->sFinalErr.as<double>();
+  st.errorHistory = out.errorHistory;
+  st.paramHistory = out.parameterHistory;
+  st.stepHistory = out.stepHistory;
+  return MMX_OK;
+}
+
+// ... with the [B][4] diagnostics of the one-launch instantiations
+int32_t bindDiagnostics(mmx_problem* pb, const mmx_gn_options* o, mmx::SolveStateDev& st) {
+  MMX_HIP(pb->sDiag.ensure(size_t(pb->B) * 4 * sizeof(float)));
+  st.diag = pb->sDiag.as<float>();
+  st.precisionBound = o->precision_bound > 0.f ? o->precision_bound : 1e-5f;
+  pb->diagValid = true;
+  return MMX_OK;
+}
+
+// Zeroes the histories that were passed (rows past an element's last iteration stay zero): step, error, parameters
+int32_t zeroHistories(const mmx_problem* pb, const mmx_gn_options* o, const SolveOutputs& out, hipStream_t s) {
+  const size_t rows = size_t(pb->B) * size_t(std::max(o->max_iterations, 0));
+  if (out.stepHistory != nullptr && rows > 0) {
+    MMX_HIP(mmx::zeroAsync(out.stepHistory, rows * 2 * sizeof(double), s));
   }
-  fst.precisionBound = o->precision_bound > 0.f ? o->precision_bound : 1e-5f;
+  if (out.errorHistory != nullptr && rows > 0) {
+    MMX_HIP(mmx::zeroAsync(out.errorHistory, rows * sizeof(double), s));
+  }
+  if (out.parameterHistory != nullptr && rows > 0) {
+    MMX_HIP(mmx::zeroAsync(out.parameterHistory, rows * size_t(pb->rig->P) * sizeof(float), s));
+  }
+  return MMX_OK;
+}
+
+// mmx_gn_options as the one-launch kernels take them.  The mixed and double executors overwrite what differs by design; the
+// wave launcher reads lambda, threshold, the iteration counts, refine and doLineSearch only (launchWave, mmx_wave.hip).
+mmx::FusedParams fusedParams(const mmx_problem* pb, const mmx_gn_options* o) {
   mmx::FusedParams fp{};
   fp.lambda = o->regularization;
   fp.threshold = o->threshold;
   fp.minIterations = o->min_iterations;
   fp.maxIterations = o->max_iterations;
-  fp.refine = 0;
+  fp.refine = refineSteps(pb);
   fp.doLineSearch = o->do_line_search;
   fp.stepRule = o->step_rule;
   fp.lmLambdaMin = o->lm_lambda_min;
   fp.lmLambdaMax = o->lm_lambda_max;
   fp.lmUp = o->lm_up;
   fp.lmDown = o->lm_down;
+  fp.trustRadius = o->trust_region_radius > 0.f ? o->trust_region_radius : 1.f;
+  return fp;
+}
+
+// Profiling aid (MMX_PHASE_CLOCKS): per-phase cycles of block 0.  armPhaseClocks leaves *clk null when they are not wanted;
+// printPhaseClocks reads them back (it synchronises the stream) and prints `count` rows under their names, with their share of
+// `total` when that is not negative.
+int32_t armPhaseClocks(mmx_problem* pb, bool withStop, hipStream_t s, long long** clk) {
+  *clk = nullptr;
+  if (!phaseClocksWanted()) {
+    return MMX_OK;
+  }
+  MMX_HIP(pb->sClk.ensure(32 * sizeof(long long)));
+  MMX_HIP(hipMemsetAsync(pb->sClk.p, 0, 32 * sizeof(long long), s));
+  *clk = pb->sClk.as<long long>();
+  if (withStop) {
+    MMX_HIP(armPhaseStop(*clk, s));
+  }
+  return MMX_OK;
+}
+
+int32_t readPhaseClocks(const long long* clk, hipStream_t s, long long (&h)[32]) {
+  MMX_HIP(hipMemcpyAsync(h, clk, sizeof(h), hipMemcpyDeviceToHost, s));
+  MMX_HIP(hipStreamSynchronize(s));
+  return MMX_OK;
+}
+
+void printPhaseClocks(const char* const* names, int count, int width, const long long* h, long long total) {
+  for (int i = 0; i < count; ++i) {
+    if (total < 0) {
+      fprintf(stderr, "  %-*s %10lld\n", width, names[i], h[i]);
+    } else {
+      fprintf(stderr, "  %-*s %10lld  %5.1f%%\n", width, names[i], h[i], 100.0 * double(h[i]) / double(total > 0 ? total : 1));
+    }
+  }
+}
+
+// ---- the executors: one per route of a single-precision stage, the mixed instantiation, the double kernel
+
+// MMX_ROUTE_WAVE: one wavefront per instance, the whole SolverT::solve loop in one launch (small rigs); numFrames > 0: one
+// wavefront per sequence (mmx_solve_frames).  No precision estimate on this route.
+int32_t runWave(mmx_problem* pb, const mmx_gn_options* o, float* theta_dev, const SolveOutputs& out, int32_t numFrames, hipStream_t s) {
+  pb->lastRoute = MMX_ROUTE_WAVE;
+  pb->diagValid = false;
+  mmx::SolveStateDev wst;
+  MMX_TRY(bindOutputs(pb, out, wst));
+  MMX_TRY(zeroHistories(pb, o, out, s));
+  const mmx::FusedParams wp = fusedParams(pb, o);
+  const SolveView sv = solveView(pb);
+  if (numFrames > 0) {
+    MMX_HIP(mmx::launchWaveFrames(sv.rig, sv.pb, sv.fd, theta_dev, wst, wp, numFrames, s));
+    return MMX_OK;
+  }
+  MMX_ZONE("wave solve: all iterations in one launch, one wavefront per instance");
+  MMX_HIP(mmx::launchWaveSolve(sv.rig, sv.pb, sv.fd, theta_dev, wst, wp, s));
+  return MMX_OK;
+}
+
+// MMX_ROUTE_FUSED: the whole SolverT::solve loop in one launch, one workgroup per instance
+int32_t runFused(mmx_problem* pb, const mmx_gn_options* o, const mmx::SolveStage& stage, float* theta_dev, const SolveOutputs& out, hipStream_t s) {
+  pb->lastRoute = MMX_ROUTE_FUSED;
+  mmx::SolveStateDev fst;
+  MMX_TRY(bindOutputs(pb, out, fst));
+  MMX_TRY(bindDiagnostics(pb, o, fst));
+  MMX_TRY(zeroHistories(pb, o, out, s));
+  mmx::FusedParams fp = fusedParams(pb, o);
+  fp.autoAbort = stage.mayAbort ? 1 : 0;
+  long long* clk = nullptr;
+  MMX_TRY(armPhaseClocks(pb, true, s, &clk));
+  {
+    MMX_ZONE("fused solve: all iterations of GaussNewtonSolverT::doIteration in one launch");
+    MMX_HIP(pb->sFusedArgs.ensure(mmx::fusedArgsBytes()));
+    const SolveView sv = solveView(pb);
+    MMX_HIP(mmx::launchFusedSolve(sv.rig, sv.pb, sv.fd, theta_dev, fst, fp, nullptr, nullptr, clk, pb->sFusedArgs.p, s));
+  }
+  if (clk != nullptr) {
+    long long h[32];
+    MMX_TRY(readPhaseClocks(clk, s, h));
+    static const char* names[24] = {"A jointParams", "B fk", "C units", "D subtree sums", "E srcTables", "F g + zero tiles",
+                                    "G combine + pull", "H cholesky(tail)", "I solve", "J tail (d0 += rho)", "K update",
+                                    "G extras: records", "G term records", "H.bc panel", "H.d mfma", "D own sums", "J jd",
+                                    "J tangent+own", "J subtree", "J rho", "J solve", "G extras: loads", "H.b load+barrier", "H.b chain"};
+    const long long tot = std::accumulate(h, h + 27, 0LL);
+    fprintf(stderr, "[mmx phase clocks, block 0, all iterations] total %lld  (termRounds %d, numComb %d, nsrc %d, n %d)\n", tot, pb->fdev.termRounds, pb->fdev.numComb, pb->fdev.nsrc, pb->fdev.n);
+    printPhaseClocks(names, 24, 16, h, tot);
+    fprintf(stderr, "  (of B fk: joint parameters %lld, local transforms %lld, pointer jumping %lld, axes = the rest of B)\n", h[26], h[24], h[25]);
+  }
+  return MMX_OK;
+}
+
+// The mixed-precision instantiation of the one-launch solve (MMX_PRECISION_MIXED, MMX_PRECISION_AUTO's second stage).  An
+// escalation stage (sel.map set) leaves the single-precision stage's histories and diagnostics for the other elements.
+int32_t runMixed(mmx_problem* pb, const mmx_gn_options* o, float* theta_dev, const SolveOutputs& out, const mmx::MixSelect& sel, hipStream_t s) {
+  MMX_ZONE("mmx_solve, mixed precision (SolverT<double>::solve around a single-precision factor)");
+  pb->lastRoute = MMX_ROUTE_FUSED;
+  mmx::SolveStateDev fst;
+  MMX_TRY(bindOutputs(pb, out, fst));
+  if (sel.map == nullptr) {
+    MMX_TRY(bindDiagnostics(pb, o, fst));
+    MMX_TRY(zeroHistories(pb, o, out, s));
+  }
+  fst.precisionBound = o->precision_bound > 0.f ? o->precision_bound : 1e-5f;
+  mmx::FusedParams fp = fusedParams(pb, o);
+  fp.refine = 0;
   fp.trustRadius = 1.f;
   fp.mixTol = pb->tuning.mixed_tolerance > 0.f ? pb->tuning.mixed_tolerance : 3e-9f;
   fp.mixMaxCg = pb->tuning.mixed_max_cg > 0 ? pb->tuning.mixed_max_cg : 12;
   long long* clk = nullptr;
-  if (phaseClocksWanted()) { // profiling aid: per-phase cycles of block 0
-    MMX_HIP(pb->sClk.ensure(32 * sizeof(long long)));
-    MMX_HIP(hipMemsetAsync(pb->sClk.p, 0, 32 * sizeof(long long), s));
-    clk = pb->sClk.as<long long>();
-    MMX_HIP(armPhaseStop(clk, s));
-  }
+  MMX_TRY(armPhaseClocks(pb, true, s, &clk));
   const SolveView sv = solveView(pb);
   MMX_HIP(mmx::launchFusedMixed(sv.rig, sv.pb, sv.fd, theta_dev, fst, fp, sel, pb->B, clk, s));
   if (clk != nullptr) {
     long long h[32];
-    MMX_HIP(hipMemcpyAsync(h, clk, sizeof(h), hipMemcpyDeviceToHost, s));
-    MMX_HIP(hipStreamSynchronize(s));
+    MMX_TRY(readPhaseClocks(clk, s, h));
     static const char* names[24] = {"-", "A-C fk + units (double)", "(reused state)", "D subtree sums", "E srcTables", "F g (double adjoint)",
                                     "G combine + pull", "H cholesky(tail)", "-", "-", "K update",
                                     "G extras: records", "G term records", "H.bc panel", "H.d mfma", "D own sums", "CG z0 solve + rz",
                                     "CG operator (double)", "CG decide + direction", "CG dots + update", "CG solve", "G extras: loads", "H.b load+barrier", "H.b chain"};
-    long long tot = 0;
-    for (int i = 0; i < 24; ++i) {
-      tot += h[i];
-    }
+    const long long tot = std::accumulate(h, h + 24, 0LL);
     fprintf(stderr, "[mmx phase clocks, MIXED, block 0, all iterations] total %lld\n", tot);
-    for (int i = 0; i < 24; ++i) {
-      fprintf(stderr, "  %-26s %10lld  %5.1f%%\n", names[i], h[i], 100.0 * double(h[i]) / double(tot > 0 ? tot : 1));
-    }
+    printPhaseClocks(names, 24, 26, h, tot);
   }
   return MMX_OK;
 }
 
-// mmx_gn_options::precision: the single-precision routes, the double instantiation on float parameters, or the first
-// followed by the second on the elements it marked
-static int32_t solveImpl(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    float* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    float* parameter_history,
-    double* step_history,
-    void* stream) {
-  if (o == nullptr || o->precision == MMX_PRECISION_F32) {
-    return solveF32Impl(pb, o, theta_dev, final_error, iterations, status, error_history, parameter_history, step_history, stream);
-  }
-  if (o->precision != MMX_PRECISION_F64 && o->precision != MMX_PRECISION_AUTO && o->precision != MMX_PRECISION_MIXED) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "unknown precision (MMX_PRECISION_*)");
-  }
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  if (theta_dev == nullptr) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "options / theta is null");
-  }
-  if (pb->tuning.route == MMX_ROUTE_WAVE) {
-    return fail(MMX_ERR_UNSUPPORTED, "MMX_ROUTE_WAVE: only MMX_PRECISION_F32 (not F64 / AUTO / MIXED)");
-  }
-  const bool mixedOk = mixedUsable(pb, o);
-  if (parameter_history != nullptr && !(o->precision == MMX_PRECISION_MIXED && mixedOk)) {
-    return fail(MMX_ERR_UNSUPPORTED, "parameter_history is single precision's (MMX_PRECISION_F32) and the mixed-precision instantiation's: the double instantiation does not record it");
-  }
-  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
-  MMX_HIP(hipSetDevice(pb->rig->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (o->precision == MMX_PRECISION_MIXED && mixedOk) {
-    return solveMixedImpl(pb, o, theta_dev, final_error, iterations, status, error_history, parameter_history, step_history, mmx::MixSelect{nullptr, nullptr, nullptr}, stream);
-  }
-  // MMX_PRECISION_AUTO with the trust region: the rule's elements are marginal by construction (it starts from lambda = 1e-10, the
-  // factor's damping floor engages on every element, and its Newton updates of lambda divide two fp32 quadratic forms: the
-  // single-precision instantiation is held to 1e-4, tests/test_gpu_trust_region.py) and the mixed instantiation does not carry the
-  // rule -- the policy's answer is the double kernel for every element, without a single-precision pass thrown away first
-  const bool autoTrust = o->precision == MMX_PRECISION_AUTO && o->step_rule == MMX_STEP_TRUST_REGION;
-  if (o->precision == MMX_PRECISION_F64 || o->precision == MMX_PRECISION_MIXED || autoTrust) { // (MIXED outside the mixed instantiation's scope: the double one)
-    // every workgroup reads its element's parameters before it writes them: in place on the caller's float array
-    return solveF64Impl(pb, o, nullptr, final_error, iterations, status, error_history, step_history, mmx::F64Select{nullptr, nullptr, theta_dev, theta_dev}, stream);
-  }
-  // (everything that can refuse or fail in the LATER stages is settled before the single-precision pass touches theta, status
-  // and the histories: the double kernel's LDS budget, its scratch, the element lists)
-  rc = preflightF64(pb);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  MMX_HIP(pb->sThetaAuto.ensure(B * P * sizeof(float)));
-  MMX_HIP(pb->sAutoMap.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sAutoCount.ensure(sizeof(int32_t)));
-  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
-  MMX_HIP(hipMemcpyAsync(pb->sThetaAuto.p, theta_dev, B * P * sizeof(float), hipMemcpyDeviceToDevice, s));
-  int32_t* st = status != nullptr ? status : pb->sStatus.as<int32_t>();
-  pb->autoAbort = mixedOk; // (the single-precision pass leaves a class its first factorisation marks: the second pass starts over anyway)
-  rc = solveF32Impl(pb, o, theta_dev, final_error, iterations, st, error_history, nullptr, step_history, stream);
-  pb->autoAbort = false;
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  // a solve without the estimate (explicit-Jacobian route, the wide route's host-driven trust region): the cue stays the damping floor
-  const int32_t mask = MMX_SOLVE_ERROR_MASK | MMX_SOLVE_PRECISION_SUSPECT | (pb->diagValid ? 0 : MMX_SOLVE_DAMPING_FLOORED);
-  MMX_HIP(mmx::launchSelectSuspect(st, pb->B, mask, pb->sAutoMap.as<int32_t>(), pb->sAutoCount.as<int32_t>(), s));
-  if (mixedOk) { // the marked elements again, from the initial parameters, by the mixed-precision instantiation ...
-    rc = solveMixedImpl(
-        pb, o, theta_dev, final_error, iterations, st, error_history, nullptr, step_history,
-        mmx::MixSelect{pb->sAutoMap.as<int32_t>(), pb->sAutoCount.as<int32_t>(), pb->sThetaAuto.as<float>()}, stream);
-    if (rc != MMX_OK) {
-      return rc;
-    }
-    // ... and the ones whose conjugate gradients ran into the step limit there (the single-precision factor is no preconditioner
-    // any more: cond x eps ~ 1 -- BASELINE configs[1] at lambda = 1e-5) or that failed, by the double instantiation
-    MMX_HIP(mmx::launchSelectSuspect(st, pb->B, MMX_SOLVE_ERROR_MASK | MMX_SOLVE_PRECISION_SUSPECT, pb->sAutoMap.as<int32_t>(), pb->sAutoCount.as<int32_t>(), s, MMX_SOLVE_MIXED));
-  }
-  return solveF64Impl(
-      pb, o, nullptr, final_error, iterations, st, error_history, step_history,
-      mmx::F64Select{pb->sAutoMap.as<int32_t>(), pb->sAutoCount.as<int32_t>(), pb->sThetaAuto.as<float>(), theta_dev}, stream);
-}
-
-static int32_t solveF32Impl(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    float* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    float* parameter_history,
-    double* step_history,
-    void* stream) {
-  MMX_ZONE("mmx_solve (SolverT::solve)");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  if (o == nullptr || theta_dev == nullptr) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "options / theta is null");
-  }
-  if (o->max_iterations < 0 || o->min_iterations < 0) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "iteration counts must be >= 0");
-  }
-  if (o->step_rule != MMX_STEP_GN_FIXED_LAMBDA && o->step_rule != MMX_STEP_LM_SCHEDULE && o->step_rule != MMX_STEP_TRUST_REGION) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "unknown step_rule");
-  }
-  if (o->do_line_search != MMX_LINE_SEARCH_NONE && o->do_line_search != MMX_LINE_SEARCH_GAUSS_NEWTON &&
-      o->do_line_search != MMX_LINE_SEARCH_DIRECTIONAL) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "unknown do_line_search rule");
-  }
-  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
-  mmx::ProblemDev ds = pb->dev; // the explicit-Jacobian solver's view: structurally zero columns dropped
-  ds.n = pb->solveN;
-  ds.enabledList = pb->dSolveListV1.as<int32_t>();
-  const int n = ds.n;
-  MMX_HIP(hipSetDevice(pb->rig->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // Systems of 129-224 solved parameters fit the fused solve only with one workgroup per CU (its instantiations for ten,
-  // twelve and fourteen 16-blocks: 55-105 KB of tiles): when the wide path's tree kernels cover the problem it is the
-  // faster route since its factor is tile-sparse (72-joint humanoid with 219 parameters, random enabled subsets, B = 4096,
-  // scripts/route_crossover.py, wide against fused solves/s: n = 105: 5.0e5 / 5.0e5, 126: 4.6e5 / 4.6e5, 136: 4.5e5 / 3.7e5,
-  // 154: 4.2e5 / 3.7e5, 166: 3.9e5 / 2.8e5, 183: 3.5e5 / 2.7e5, 219: 3.3e5 / 2.2e5) -- up to eight blocks (two or three
-  // workgroups per CU) the fused solve stays.  mmx_tuning::route pins either.
-  const int32_t route = pb->tuning.route;
-  if (route == MMX_ROUTE_WAVE) {
-    // one wavefront per instance, the whole SolverT::solve loop in one launch (small rigs; taken only when pinned)
-    if (const char* why = waveRefusal(pb, o)) {
-      return fail(MMX_ERR_UNSUPPORTED, why);
-    }
-    if (step_history != nullptr) {
-      return fail(MMX_ERR_UNSUPPORTED, "MMX_ROUTE_WAVE: step_history is the LM schedule's");
-    }
-    pb->lastRoute = MMX_ROUTE_WAVE;
-    pb->diagValid = false; // (no precision estimate on this route)
-    MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
-    MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
-    MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
-    mmx::SolveStateDev wst{};
-    wst.iterations = iterations != nullptr ? iterations : pb->sIters.as<int32_t>();
-    wst.status = status != nullptr ? status : pb->sStatus.as<int32_t>();
-    wst.finalError = final_error != nullptr ? final_error : pb->sFinalErr.as<double>();
-    wst.errorHistory = error_history;
-    wst.paramHistory = parameter_history;
-    if (error_history != nullptr && o->max_iterations > 0) {
-      MMX_HIP(mmx::zeroAsync(error_history, B * size_t(o->max_iterations) * sizeof(double), s));
-    }
-    if (parameter_history != nullptr && o->max_iterations > 0) {
-      MMX_HIP(mmx::zeroAsync(parameter_history, B * size_t(o->max_iterations) * P * sizeof(float), s));
-    }
-    mmx::FusedParams wp{};
-    wp.lambda = o->regularization;
-    wp.threshold = o->threshold;
-    wp.minIterations = o->min_iterations;
-    wp.maxIterations = o->max_iterations;
-    wp.refine = refineSteps(pb);
-    wp.doLineSearch = o->do_line_search;
-    wp.stepRule = o->step_rule;
-    MMX_ZONE("wave solve: all iterations in one launch, one wavefront per instance");
-    const SolveView sv = solveView(pb);
-    MMX_HIP(mmx::launchWaveSolve(sv.rig, sv.pb, sv.fd, theta_dev, wst, wp, s));
-    return MMX_OK;
-  }
-  const bool forceWide = route == MMX_ROUTE_WIDE;
-  const bool trust = o->step_rule == MMX_STEP_TRUST_REGION;
-  // (the trust region's re-solve loops live in the one-launch solve; the wide route drives them from the host, several
-  // small kernels per trust step: it takes the rule only where the fused solve cannot -- more than 224 solved
-  // parameters, further joint error functions / ellipsoid limits -- or when pinned)
-  const bool trustNeedsWide = trust && (!fusedUsable(pb) || pb->fdev.GT > 0);
-  const bool preferWide = (forceWide || trustNeedsWide || (!trust && mmx::fusedBlocksFor(pb->fdev.n) >= 10)) &&
-      treeNormalEquationsUsable(pb) && route != MMX_ROUTE_FUSED && route != MMX_ROUTE_EXPLICIT_JACOBIAN;
-  const bool legacy = route == MMX_ROUTE_EXPLICIT_JACOBIAN;
-  const bool takeFused = fusedUsable(pb) && !legacy && !preferWide && !(pb->fdev.GT > 0 && o->step_rule == MMX_STEP_TRUST_REGION);
-  if (route == MMX_ROUTE_FUSED && !takeFused) {
-    return fail(MMX_ERR_UNSUPPORTED, "MMX_ROUTE_FUSED: the problem does not fit the one-launch solve (more than 224 solved parameters, or its tables beyond the LDS budget)");
-  }
-  if (route == MMX_ROUTE_WIDE && !preferWide) {
-    return fail(MMX_ERR_UNSUPPORTED, "MMX_ROUTE_WIDE: the problem is outside the tree kernels' scope");
-  }
-  if (takeFused) {
-    pb->lastRoute = MMX_ROUTE_FUSED;
-    // fused path: the whole SolverT::solve loop in one launch, one workgroup per instance
-    MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
-    MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
-    MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
-    mmx::SolveStateDev fst{};
-    fst.done = nullptr;
-    fst.iterations = iterations != nullptr ? iterations : pb->sIters.as<int32_t>();
-    fst.status = status != nullptr ? status : pb->sStatus.as<int32_t>();
-    fst.lastError = nullptr;
-    fst.finalError = final_error != nullptr ? final_error : pb->sFinalErr.as<double>();
-    fst.errorHistory = error_history;
-    fst.paramHistory = parameter_history;
-    fst.stepHistory = step_history;
-    MMX_HIP(pb->sDiag.ensure(B * 4 * sizeof(float)));
-    fst.diag = pb->sDiag.as<float>();
-    fst.precisionBound = o->precision_bound > 0.f ? o->precision_bound : 1e-5f;
-    pb->diagValid = true;
-    if (step_history != nullptr && o->max_iterations > 0) {
-      MMX_HIP(mmx::zeroAsync(step_history, B * size_t(o->max_iterations) * 2 * sizeof(double), s));
-    }
-    if (error_history != nullptr && o->max_iterations > 0) {
-      MMX_HIP(mmx::zeroAsync(error_history, B * size_t(o->max_iterations) * sizeof(double), s));
-    }
-    if (parameter_history != nullptr && o->max_iterations > 0) {
-      MMX_HIP(mmx::zeroAsync(parameter_history, B * size_t(o->max_iterations) * P * sizeof(float), s));
-    }
-    mmx::FusedParams fp{};
-    fp.lambda = o->regularization;
-    fp.threshold = o->threshold;
-    fp.minIterations = o->min_iterations;
-    fp.maxIterations = o->max_iterations;
-    fp.refine = refineSteps(pb);
-    fp.doLineSearch = o->do_line_search;
-    fp.stepRule = o->step_rule;
-    fp.lmLambdaMin = o->lm_lambda_min;
-    fp.lmLambdaMax = o->lm_lambda_max;
-    fp.lmUp = o->lm_up;
-    fp.lmDown = o->lm_down;
-    fp.trustRadius = o->trust_region_radius > 0.f ? o->trust_region_radius : 1.f;
-    fp.autoAbort = pb->autoAbort ? 1 : 0;
-    long long* clk = nullptr;
-    if (phaseClocksWanted()) { // profiling aid: per-phase cycles of block 0
-      MMX_HIP(pb->sClk.ensure(32 * sizeof(long long)));
-      MMX_HIP(hipMemsetAsync(pb->sClk.p, 0, 32 * sizeof(long long), s));
-      clk = pb->sClk.as<long long>();
-      MMX_HIP(armPhaseStop(clk, s));
-    }
-    {
-      MMX_ZONE("fused solve: all iterations of GaussNewtonSolverT::doIteration in one launch");
-      MMX_HIP(pb->sFusedArgs.ensure(mmx::fusedArgsBytes()));
-      const SolveView sv = solveView(pb);
-      MMX_HIP(mmx::launchFusedSolve(sv.rig, sv.pb, sv.fd, theta_dev, fst, fp, nullptr, nullptr, clk, pb->sFusedArgs.p, s));
-    }
-    if (clk != nullptr) {
-      long long h[32];
-      MMX_HIP(hipMemcpyAsync(h, clk, sizeof(h), hipMemcpyDeviceToHost, s));
-      MMX_HIP(hipStreamSynchronize(s));
-      static const char* names[24] = {"A jointParams", "B fk", "C units", "D subtree sums", "E srcTables", "F g + zero tiles",
-                                      "G combine + pull", "H cholesky(tail)", "I solve", "J tail (d0 += rho)", "K update",
-                                      "G extras: records", "G term records", "H.bc panel", "H.d mfma", "D own sums", "J jd",
-                                      "J tangent+own", "J subtree", "J rho", "J solve", "G extras: loads", "H.b load+barrier", "H.b chain"};
-      long long tot = h[24] + h[25] + h[26];
-      for (int i = 0; i < 24; ++i) {
-        tot += h[i];
-      }
-      fprintf(stderr, "[mmx phase clocks, block 0, all iterations] total %lld  (termRounds %d, numComb %d, nsrc %d, n %d)\n", tot, pb->fdev.termRounds, pb->fdev.numComb, pb->fdev.nsrc, pb->fdev.n);
-      for (int i = 0; i < 24; ++i) {
-        fprintf(stderr, "  %-16s %10lld  %5.1f%%\n", names[i], h[i], 100.0 * double(h[i]) / double(tot > 0 ? tot : 1));
-      }
-      fprintf(stderr, "  (of B fk: joint parameters %lld, local transforms %lld, pointer jumping %lld, axes = the rest of B)\n", h[26], h[24], h[25]);
-    }
-    return MMX_OK;
-  }
-  if (trust && !(preferWide && treeNormalEquationsUsable(pb) && route != MMX_ROUTE_EXPLICIT_JACOBIAN)) {
-    return fail(MMX_ERR_UNSUPPORTED, "MMX_STEP_TRUST_REGION: available in the one-launch solve and on the wide route (tree kernels); this problem takes neither (MMX_ROUTE_EXPLICIT_JACOBIAN, or outside the tree kernels' scope)");
-  }
-  if (n > mmx::kMaxSolved) {
-    return fail(MMX_ERR_UNSUPPORTED, "more than 2048 solved parameters (kMaxModelParams; 512 on the tree routes, the explicit-Jacobian route takes the rest)");
-  }
-  // Wide systems (the in-LDS Cholesky step does not fit) inside the tree kernels' scope: normal equations from the tree
-  // moments, left-looking factor in HBM, refinement through the tree.  No dense J is written or read.
-  // MMX_ROUTE_EXPLICIT_JACOBIAN (and problems outside the tree kernels' scope): dense J, J^T J on the matrix cores,
-  // the refinement streams J.
-  const bool wide = mmx::choleskyStepLdsBytes(ds.n, ds.M) > 160 * 1024; // (the in-LDS Cholesky step does not fit)
-  const bool treeRefine = (wide || preferWide) && treeNormalEquationsUsable(pb) && route != MMX_ROUTE_EXPLICIT_JACOBIAN;
-  if (route == MMX_ROUTE_WIDE && !treeRefine) {
-    return fail(MMX_ERR_UNSUPPORTED, "MMX_ROUTE_WIDE: the tree-refined wide solve is not available for this problem");
-  }
-  pb->lastRoute = treeRefine ? MMX_ROUTE_WIDE : MMX_ROUTE_EXPLICIT_JACOBIAN;
-  rc = ensureStepScratch(pb, !treeRefine);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  MMX_HIP(pb->sThetaInit.ensure(B * P * sizeof(float)));
-  MMX_HIP(pb->sDone.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sLastErr.ensure(B * sizeof(double)));
-  MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
-  mmx::SolveStateDev st{};
-  st.done = pb->sDone.as<int32_t>();
-  st.iterations = iterations != nullptr ? iterations : pb->sIters.as<int32_t>();
-  st.status = status != nullptr ? status : pb->sStatus.as<int32_t>();
-  st.lastError = pb->sLastErr.as<double>();
-  st.finalError = final_error != nullptr ? final_error : pb->sFinalErr.as<double>();
-  st.errorHistory = error_history;
-  st.paramHistory = nullptr; // (explicit-Jacobian path: the history is copied after every iteration, below)
-  st.stepHistory = step_history;
-  pb->diagValid = false; // (the wide route's estimate: below, where its kernels are set up)
-  if (step_history != nullptr && o->max_iterations > 0) {
-    MMX_HIP(mmx::zeroAsync(step_history, B * size_t(o->max_iterations) * 2 * sizeof(double), s));
-  }
-  if (error_history != nullptr && o->max_iterations > 0) {
-    MMX_HIP(mmx::zeroAsync(error_history, B * size_t(o->max_iterations) * sizeof(double), s));
-  }
-  MMX_HIP(hipMemcpyAsync(pb->sThetaInit.p, theta_dev, B * P * sizeof(float), hipMemcpyDeviceToDevice, s));
-  const bool deferred = trust || o->do_line_search != 0 || o->step_rule == MMX_STEP_LM_SCHEDULE;
-  const bool schedule = trust || o->step_rule == MMX_STEP_LM_SCHEDULE; // per-instance damping
-  if (deferred) {
-    MMX_HIP(pb->sDelta.ensure(B * size_t(std::max(n, 1)) * sizeof(float)));
-    MMX_HIP(pb->sStepIter.ensure(B * sizeof(int32_t)));
-    MMX_HIP(mmx::zeroAsync(pb->sStepIter.p, B * sizeof(int32_t), s));
-  }
-  if (schedule) {
-    MMX_HIP(pb->sLambda.ensure(B * sizeof(float)));
-  }
-  // the precision estimate on the wide route (tree kernels + tile factor + finish stage); the trust region's host-driven
-  // re-factorisations and the explicit-Jacobian route keep MMX_SOLVE_DAMPING_FLOORED as their cue
-  const bool wideDiag = treeRefine && !trust && refineSteps(pb) > 0;
-  if (wideDiag) {
-    MMX_HIP(pb->sDiag.ensure(B * 4 * sizeof(float)));
-    MMX_HIP(pb->sDiagAcc.ensure(B * 4 * sizeof(float)));
-    MMX_HIP(pb->sDiagErr0.ensure(B * sizeof(float)));
-    st.diag = pb->sDiag.as<float>();
-    st.precisionBound = o->precision_bound > 0.f ? o->precision_bound : 1e-5f;
-    pb->diagValid = true;
-  }
-  MMX_HIP(mmx::launchSolveInit(st, pb->B, schedule ? pb->sLambda.as<float>() : nullptr, o->regularization, s, wideDiag ? pb->sDiagAcc.as<float>() : nullptr));
-  mmx::StepParams sp{};
-  sp.diagAcc = wideDiag ? pb->sDiagAcc.as<float>() : nullptr;
-  sp.diagErr0 = wideDiag ? pb->sDiagErr0.as<float>() : nullptr;
-  sp.lambda = o->regularization;
-  sp.threshold = o->threshold;
-  sp.minIterations = o->min_iterations;
-  sp.maxIterations = o->max_iterations;
-  sp.refine = refineSteps(pb);
-  sp.tileMasks = pb->dTileMasks.as<uint32_t>();
-  sp.numTiles = int32_t(pb->tileMasks.tiles.size());
-  sp.delta = deferred ? pb->sDelta.as<float>() : nullptr;
-  sp.stepIter = deferred ? pb->sStepIter.as<int32_t>() : nullptr;
-  sp.lambdaPer = schedule ? pb->sLambda.as<float>() : nullptr;
-  sp.stepHistory = step_history;
-  sp.doLineSearch = trust ? 0 : o->do_line_search; // (the trust region reads neither do_line_search nor regularization)
-  sp.stepRule = o->step_rule;
-  if (trust) {
-    MMX_HIP(pb->sTrust.ensure(B * 6 * sizeof(int32_t) + 16));
-    char* base = static_cast<char*>(pb->sTrust.p);
-    sp.tr.lambda = reinterpret_cast<float*>(base);
-    sp.tr.radius = reinterpret_cast<float*>(base + B * 4);
-    sp.tr.phase = reinterpret_cast<int32_t*>(base + B * 8);
-    sp.tr.newton = reinterpret_cast<int32_t*>(base + B * 12);
-    sp.tr.step = reinterpret_cast<int32_t*>(base + B * 16);
-    sp.tr.mask = reinterpret_cast<int32_t*>(base + B * 20);
-    sp.tr.active = reinterpret_cast<int32_t*>(base + B * 24);
-    MMX_HIP(mmx::launchTrustInit(sp.tr, pb->B, o->trust_region_radius > 0.f ? o->trust_region_radius : 1.f, s));
-  }
-  sp.lmLambdaMin = o->lm_lambda_min;
-  sp.lmLambdaMax = o->lm_lambda_max;
-  sp.lmUp = o->lm_up;
-  sp.lmDown = o->lm_down;
-  if (phaseClocksWanted()) {
-    MMX_HIP(pb->sClk.ensure(32 * sizeof(long long)));
-    MMX_HIP(hipMemsetAsync(pb->sClk.p, 0, 32 * sizeof(long long), s));
-    sp.clk = pb->sClk.as<long long>();
-  }
-  float* factorScratch = nullptr; // wide systems: the left-looking Cholesky step keeps L in its own tile-major scratch
-  if (wide || treeRefine) {
-    MMX_HIP(pb->sFactor.ensure(size_t(B) * mmx::choleskyFactorFloats(ds.n) * sizeof(float)));
-    factorScratch = pb->sFactor.as<float>();
-  }
-  const size_t NPs = (size_t(n) + 15) & ~size_t(15);
-  float* genState = nullptr; // J_g of the further joint error functions / ellipsoid limits, tree kernels' hand-over
-  if (treeRefine) {
-    // (H travels tile-major on this route: NB (NB + 1) / 2 tiles of 256 floats, more than n^2 for small systems)
-    MMX_HIP(pb->sJtj.ensure(std::max(size_t(B) * size_t(pb->dev.n) * size_t(pb->dev.n), size_t(B) * mmx::choleskyFactorFloats(ds.n)) * sizeof(float)));
-    MMX_HIP(pb->sTreeState.ensure(size_t(B) * mmx::treeStateFloats(pb->rig->J, pb->fdev.U) * sizeof(float)));
-    MMX_HIP(pb->sDvec.ensure(size_t(B) * NPs * sizeof(float)));
-    MMX_HIP(pb->sRhoVec.ensure(size_t(B) * NPs * sizeof(float)));
-    MMX_HIP(pb->sRefState.ensure(size_t(B) * sizeof(int32_t)));
-    if (pb->fdev.GT > 0) {
-      MMX_HIP(pb->sGenState.ensure(size_t(B) * mmx::treeGenStateFloats(pb->fdev.n, pb->fdev.genRows) * sizeof(float)));
-      genState = pb->sGenState.as<float>();
-    }
-  }
-  const SolveView sv = solveView(pb); // (the tree kernels' descriptors; everything else on this route keeps the full rig)
-  for (int it = 0; it < o->max_iterations; ++it) { // solver.cpp:89
-    sp.iteration = it;
-    MMX_ZONE("GaussNewtonSolverT::doIteration");
-    if (treeRefine) {
-      {
-        MMX_ZONE("Get JtJ and JtR");
-        MMX_HIP(mmx::launchTreeNormalEquations(
-            sv.rig, sv.pb, sv.fd, theta_dev, pb->sJtj.as<float>(), pb->sJtr.as<float>(), st.done, pb->sErr.as<double>(),
-            pb->sTreeState.as<float>(), sp.clk != nullptr ? sp.clk + 8 : nullptr, genState, true, s));
-      }
-      MMX_ZONE("Dense gauss newton step");
-      // factor + first solve, then up to three refinement rounds; an instance whose correction fell below 1e-3 of its step
-      // applies the step and sits out the remaining rounds (its workgroups return at once)
-      auto linearSolve = [&](const mmx::SolveStateDev& who) -> int32_t {
-        MMX_HIP(mmx::launchCholeskyFactorTiled(
-            ds, pb->rig->P, pb->sJtj.as<float>(), pb->sJtr.as<float>(), factorScratch, pb->sDvec.as<float>(), pb->sRefState.as<int32_t>(),
-            pb->sErr.as<double>(), theta_dev, who, sp, s));
-        for (int round = 0; round < sp.refine; ++round) {
-          MMX_HIP(mmx::launchTreeRefine(
-              sv.rig, sv.pb, sv.fd, theta_dev, pb->sTreeState.as<float>(), genState, pb->sDvec.as<float>(), pb->sRhoVec.as<float>(), pb->sRefState.as<int32_t>(),
-              sp.lambda, sp.lambdaPer, s));
-          MMX_HIP(mmx::launchCholeskyFinishTiled(
-              ds, pb->rig->P, factorScratch, pb->sDvec.as<float>(), pb->sRhoVec.as<float>(), pb->sRefState.as<int32_t>(), pb->sErr.as<double>(),
-              theta_dev, who, sp, round, s));
-        }
-        return MMX_OK;
-      };
-      if (trust) {
-        // TrustRegionQRT::doIteration (trust_region_qr.cpp:52-270) from the host: per pass, the instances whose damping
-        // changed factor and solve, every instance with a step on the table decides (try it, or a Newton update of lambda
-        // first), the ready ones run their trial.  At most ten trust steps of up to four solves each; the loop ends as
-        // soon as no instance is left in the iteration (one 4-byte read-back per pass).
-        MMX_ZONE("TrustRegionQR: trust steps");
-        MMX_HIP(mmx::launchTrustBegin(sp.tr, st, sp.lambdaPer, pb->B, s));
-        mmx::SolveStateDev masked = st;
-        masked.done = sp.tr.mask;
-        for (int pass = 0; pass < 40; ++pass) {
-          rc = linearSolve(masked);
-          if (rc != MMX_OK) {
-            return rc;
-          }
-          MMX_HIP(mmx::launchTrustDecide(ds, factorScratch, pb->sJtr.as<float>(), pb->sErr.as<double>(), st, sp, s));
-          MMX_HIP(mmx::zeroAsync(sp.tr.active, sizeof(int32_t), s));
-          MMX_HIP(mmx::launchStepUpdate(pb->rigDev, ds, theta_dev, pb->sJtr.as<float>(), pb->sErr.as<double>(), sp, s));
-          int32_t active = 0;
-          MMX_HIP(hipMemcpyAsync(&active, sp.tr.active, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-          MMX_HIP(hipStreamSynchronize(s));
-          if (active == 0) {
-            break;
-          }
-        }
-        MMX_HIP(mmx::launchTrustEnd(st, sp, pb->sErr.as<double>(), pb->B, s));
-      } else {
-        rc = linearSolve(st);
-        if (rc != MMX_OK) {
-          return rc;
-        }
-      }
-    } else {
-      {
-        MMX_ZONE("Get JtJ and JtR");
-        MMX_HIP(mmx::launchFkJacobian(
-            pb->rigDev, pb->dev, theta_dev, pb->sJac.as<float>(), pb->sRes.as<float>(), pb->sErr.as<double>(), nullptr, st.done, s, nullptr, nullptr, true));
-        MMX_HIP(mmx::launchNormalEquations(
-            ds, pb->rig->P, pb->sJac.as<float>(), pb->sRes.as<float>(), pb->sJtj.as<float>(), pb->sJtr.as<float>(), st.done, wide, s));
-      }
-      {
-        MMX_ZONE("Dense gauss newton step");
-        MMX_HIP(mmx::launchCholeskyStep(
-            ds, pb->rig->P, pb->sJac.as<float>(), pb->sRes.as<float>(), pb->sJtj.as<float>(), pb->sJtr.as<float>(), pb->sErr.as<double>(),
-            theta_dev, st, sp, factorScratch, s));
-      }
-    }
-    if (deferred && !trust) {
-      MMX_ZONE("Line search");
-      MMX_HIP(mmx::launchStepUpdate(pb->rigDev, ds, theta_dev, pb->sJtr.as<float>(), pb->sErr.as<double>(), sp, s));
-    }
-    if (parameter_history != nullptr) { // parameters after iteration `it`, every element (rows past an element's last iteration are zeroed at the end)
-      MMX_HIP(hipMemcpy2DAsync(
-          parameter_history + size_t(it) * P, size_t(o->max_iterations) * P * sizeof(float), theta_dev, P * sizeof(float), P * sizeof(float), B,
-          hipMemcpyDeviceToDevice, s));
-    }
-  }
-  if (parameter_history != nullptr) {
-    MMX_HIP(mmx::launchParamHistoryFinalize(parameter_history, st.iterations, pb->B, o->max_iterations, pb->rig->P, s));
-  }
-  MMX_HIP(mmx::launchSolveFinalize(theta_dev, pb->sThetaInit.as<float>(), pb->rig->P, st, pb->B, s, sp.diagAcc));
-  if (sp.clk != nullptr) {
-    long long h[16];
-    MMX_HIP(hipMemcpyAsync(h, sp.clk, sizeof(h), hipMemcpyDeviceToHost, s));
-    MMX_HIP(hipStreamSynchronize(s));
-    static const char* names[8] = {"load H / fence", "factor (in-HBM: write-back + trailing)", "solve", "refine: w = r - J d", "refine: rho = J^T w", "refine: solve", "factor: panel load (in-HBM)", "factor: panel chain (in-HBM)"};
-    fprintf(stderr, "[mmx phase clocks, choleskyStepKernel block 0, all iterations] n = %d\n", n);
-    for (int i = 0; i < 8; ++i) {
-      fprintf(stderr, "  %-40s %10lld\n", names[i], h[i]);
-    }
-    if (treeRefine) {
-      static const char* tnames[8] = {"tree NE: load", "tree NE: A, B forward kinematics", "tree NE: C units + hand-over", "tree NE: D own sums",
-                                      "tree NE: D subtree sums", "tree NE: E slot tables", "tree NE: F, G tiles", "tree NE: G extras"};
-      for (int i = 0; i < 8; ++i) {
-        fprintf(stderr, "  %-40s %10lld\n", tnames[i], h[8 + i]);
-      }
-    }
-  }
-  return MMX_OK;
-}
-
-namespace {
 // mmx::F64AssemblyList for chunks of `uc` units (mmx::buildF64AssemblyListHost), uploaded
 int32_t buildF64AssemblyList(mmx_problem* pb, int32_t uc) {
   mmx::F64AssemblyListHost h;
@@ -2500,7 +2013,417 @@ int32_t buildF64AssemblyList(mmx_problem* pb, int32_t uc) {
   pb->f64ListUnitsPerChunk = uc;
   return MMX_OK;
 }
+
+bool residentF64(const mmx_problem* pb) {
+  return mmx::solveF64IsResident(pb->rig->J, pb->rig->P, pb->U, pb->solveN, pb->dev.G + pb->dev.NE, pb->dev.rowsJoint - 3 * pb->U);
+}
+
+// The scratch form of the double kernel: dense J and H of every element in a global scratch of the problem.  MMX_PRECISION_AUTO
+// allocates it before its single-precision stage, so that a failure of the later stage leaves the caller's arrays untouched.
+int32_t ensureF64Scratch(mmx_problem* pb) {
+  const size_t B = size_t(pb->B), n = size_t(pb->solveN), M = size_t(pb->dev.rowsJoint);
+  if (!residentF64(pb)) {
+    MMX_HIP(pb->sJacF64.ensure(std::max<size_t>(B * n * M, 1) * sizeof(double)));
+    MMX_HIP(pb->sHessF64.ensure(std::max<size_t>(B * n * n, 1) * sizeof(double)));
+  }
+  return MMX_OK;
+}
+
+// The double instantiation (mmx_solve_f64; MMX_PRECISION_F64 and the last stage of MMX_PRECISION_AUTO of mmx_solve).
+// theta_dev: double [B][P] in / out, or null when `select` carries float arrays.  It records no route, and no parameter
+// history (the plan refuses a call that passes one); an escalation stage (select.map set) leaves the earlier stages' histories for the other elements.
+int32_t runDouble(mmx_problem* pb, const mmx_gn_options* o, double* theta_dev, const SolveOutputs& out, const mmx::F64Select& select, hipStream_t s) {
+  MMX_ZONE("mmx_solve_f64 (SolverT<double>::solve)");
+  const size_t B = size_t(pb->B), n = size_t(pb->solveN);
+  const int genRowsF64 = pb->dev.rowsJoint - 3 * pb->U;
+  MMX_TRY(ensureF64Scratch(pb));
+  const bool trustF64 = o->step_rule == MMX_STEP_TRUST_REGION;
+  if (trustF64) {
+    MMX_HIP(pb->sHess2F64.ensure(std::max<size_t>(B * n * n, 1) * sizeof(double)));
+  }
+  mmx::SolveStateDev st;
+  MMX_TRY(bindOutputs(pb, out, st));
+  if (select.map == nullptr && o->max_iterations > 0) { // (this path zeroes the error history first and records no parameter history)
+    const size_t rows = B * size_t(o->max_iterations);
+    if (out.errorHistory != nullptr) {
+      MMX_HIP(mmx::zeroAsync(out.errorHistory, rows * sizeof(double), s));
+    }
+    if (out.stepHistory != nullptr) {
+      MMX_HIP(mmx::zeroAsync(out.stepHistory, rows * 2 * sizeof(double), s));
+    }
+  }
+  mmx::FusedParams fp = fusedParams(pb, o);
+  fp.refine = 0;
+  mmx::F64AssemblyList alist{nullptr, nullptr, nullptr, 0};
+  if (residentF64(pb) && pb->dev.instPosParent == nullptr && pb->dev.instOriParent == nullptr && pb->rig->J < 4096 && pb->solveN <= 4096) {
+    const int32_t uc = mmx::solveF64ResidentChunkRows(pb->rig->J, pb->rig->P, pb->U, pb->solveN, pb->dev.G + pb->dev.NE, genRowsF64) / 3;
+    if (uc > 0 && uc <= 64) {
+      if (pb->f64ListUnitsPerChunk != uc) {
+        MMX_TRY(buildF64AssemblyList(pb, uc));
+      }
+      alist = mmx::F64AssemblyList{pb->dF64Groups.as<uint2>(), pb->dF64Extra.as<int32_t>(), pb->dF64ChunkStart.as<int32_t>(), uc};
+    }
+  }
+  MMX_HIP(mmx::launchSolveF64(
+      pb->rigDev, pb->dev, pb->dSolveListF64.as<int32_t>(), pb->solveN, theta_dev, st, fp, pb->sJacF64.as<double>(), pb->sHessF64.as<double>(), trustF64 ? pb->sHess2F64.as<double>() : nullptr, s, alist, select));
+  return MMX_OK;
+}
+
+// ---- the host-driven routes (MMX_ROUTE_WIDE, MMX_ROUTE_EXPLICIT_JACOBIAN): several kernels per iteration
+
+struct HostDriven {
+  mmx::ProblemDev ds; // the explicit-Jacobian solver's view: structurally zero columns dropped
+  mmx::SolveStateDev st;
+  mmx::StepParams sp;
+  float* factorScratch = nullptr; // wide systems: the left-looking Cholesky step keeps L in its own tile-major scratch
+  float* genState = nullptr; // J_g of the further joint error functions / ellipsoid limits, tree kernels' hand-over
+  SolveView sv; // (the tree kernels' descriptors; everything else on these routes keeps the full rig)
+};
+
+// Scratch, solve state and step parameters of a host-driven solve; the initial parameters are kept for the finalize kernel
+int32_t prepareHostDriven(
+    mmx_problem* pb, const mmx_gn_options* o, const mmx::SolveStage& stage, const float* theta_dev, const SolveOutputs& out, hipStream_t s, HostDriven& hd) {
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
+  const bool trust = o->step_rule == MMX_STEP_TRUST_REGION;
+  hd.ds = pb->dev;
+  hd.ds.n = pb->solveN;
+  hd.ds.enabledList = pb->dSolveListV1.as<int32_t>();
+  const int n = hd.ds.n;
+  MMX_TRY(ensureStepScratch(pb, !stage.treeRefine));
+  MMX_HIP(pb->sThetaInit.ensure(B * P * sizeof(float)));
+  MMX_HIP(pb->sDone.ensure(B * sizeof(int32_t)));
+  MMX_HIP(pb->sLastErr.ensure(B * sizeof(double)));
+  SolveOutputs bound = out;
+  bound.parameterHistory = nullptr; // (copied after every iteration and finalised: iterateHostDriven, runHostDriven)
+  mmx::SolveStateDev& st = hd.st;
+  MMX_TRY(bindOutputs(pb, bound, st));
+  st.done = pb->sDone.as<int32_t>();
+  st.lastError = pb->sLastErr.as<double>();
+  pb->diagValid = false; // (the wide route's estimate: below)
+  MMX_TRY(zeroHistories(pb, o, bound, s));
+  MMX_HIP(hipMemcpyAsync(pb->sThetaInit.p, theta_dev, B * P * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (stage.deferred) {
+    MMX_HIP(pb->sDelta.ensure(B * size_t(std::max(n, 1)) * sizeof(float)));
+    MMX_HIP(pb->sStepIter.ensure(B * sizeof(int32_t)));
+    MMX_HIP(mmx::zeroAsync(pb->sStepIter.p, B * sizeof(int32_t), s));
+  }
+  if (stage.schedule) {
+    MMX_HIP(pb->sLambda.ensure(B * sizeof(float)));
+  }
+  if (stage.wideDiag) { // the precision estimate on the wide route (tree kernels + tile factor + finish stage)
+    MMX_HIP(pb->sDiagAcc.ensure(B * 4 * sizeof(float)));
+    MMX_HIP(pb->sDiagErr0.ensure(B * sizeof(float)));
+    MMX_TRY(bindDiagnostics(pb, o, st));
+  }
+  MMX_HIP(mmx::launchSolveInit(st, pb->B, stage.schedule ? pb->sLambda.as<float>() : nullptr, o->regularization, s, stage.wideDiag ? pb->sDiagAcc.as<float>() : nullptr));
+  mmx::StepParams& sp = hd.sp;
+  sp = mmx::StepParams{};
+  sp.diagAcc = stage.wideDiag ? pb->sDiagAcc.as<float>() : nullptr;
+  sp.diagErr0 = stage.wideDiag ? pb->sDiagErr0.as<float>() : nullptr;
+  sp.lambda = o->regularization;
+  sp.threshold = o->threshold;
+  sp.minIterations = o->min_iterations;
+  sp.maxIterations = o->max_iterations;
+  sp.refine = refineSteps(pb);
+  sp.tileMasks = pb->dTileMasks.as<uint32_t>();
+  sp.numTiles = int32_t(pb->tileMasks.tiles.size());
+  sp.delta = stage.deferred ? pb->sDelta.as<float>() : nullptr;
+  sp.stepIter = stage.deferred ? pb->sStepIter.as<int32_t>() : nullptr;
+  sp.lambdaPer = stage.schedule ? pb->sLambda.as<float>() : nullptr;
+  sp.stepHistory = out.stepHistory;
+  sp.doLineSearch = trust ? 0 : o->do_line_search; // (the trust region reads neither do_line_search nor regularization)
+  sp.stepRule = o->step_rule;
+  if (trust) {
+    MMX_HIP(pb->sTrust.ensure(B * 6 * sizeof(int32_t) + 16));
+    char* base = static_cast<char*>(pb->sTrust.p);
+    sp.tr.lambda = reinterpret_cast<float*>(base);
+    sp.tr.radius = reinterpret_cast<float*>(base + B * 4);
+    sp.tr.phase = reinterpret_cast<int32_t*>(base + B * 8);
+    sp.tr.newton = reinterpret_cast<int32_t*>(base + B * 12);
+    sp.tr.step = reinterpret_cast<int32_t*>(base + B * 16);
+    sp.tr.mask = reinterpret_cast<int32_t*>(base + B * 20);
+    sp.tr.active = reinterpret_cast<int32_t*>(base + B * 24);
+    MMX_HIP(mmx::launchTrustInit(sp.tr, pb->B, o->trust_region_radius > 0.f ? o->trust_region_radius : 1.f, s));
+  }
+  sp.lmLambdaMin = o->lm_lambda_min;
+  sp.lmLambdaMax = o->lm_lambda_max;
+  sp.lmUp = o->lm_up;
+  sp.lmDown = o->lm_down;
+  MMX_TRY(armPhaseClocks(pb, false, s, &sp.clk));
+  if (stage.wide || stage.treeRefine) {
+    MMX_HIP(pb->sFactor.ensure(B * mmx::choleskyFactorFloats(n) * sizeof(float)));
+    hd.factorScratch = pb->sFactor.as<float>();
+  }
+  if (stage.treeRefine) {
+    // (H travels tile-major on this route: NB (NB + 1) / 2 tiles of 256 floats, more than n^2 for small systems)
+    const size_t NPs = (size_t(n) + 15) & ~size_t(15);
+    MMX_HIP(pb->sJtj.ensure(std::max(B * size_t(pb->dev.n) * size_t(pb->dev.n), B * mmx::choleskyFactorFloats(n)) * sizeof(float)));
+    MMX_HIP(pb->sTreeState.ensure(B * mmx::treeStateFloats(pb->rig->J, pb->fdev.U) * sizeof(float)));
+    MMX_HIP(pb->sDvec.ensure(B * NPs * sizeof(float)));
+    MMX_HIP(pb->sRhoVec.ensure(B * NPs * sizeof(float)));
+    MMX_HIP(pb->sRefState.ensure(B * sizeof(int32_t)));
+    if (pb->fdev.GT > 0) {
+      MMX_HIP(pb->sGenState.ensure(B * mmx::treeGenStateFloats(pb->fdev.n, pb->fdev.genRows) * sizeof(float)));
+      hd.genState = pb->sGenState.as<float>();
+    }
+  }
+  hd.sv = solveView(pb);
+  return MMX_OK;
+}
+
+// The wide route's linear solve for the instances `who` leaves in: factor + first solve, then up to three refinement rounds;
+// an instance whose correction fell below 1e-3 of its step applies the step and sits out the remaining rounds (its workgroups
+// return at once)
+int32_t treeLinearSolve(mmx_problem* pb, const HostDriven& hd, const mmx::SolveStateDev& who, float* theta_dev, hipStream_t s) {
+  const mmx::StepParams& sp = hd.sp;
+  MMX_HIP(mmx::launchCholeskyFactorTiled(
+      hd.ds, pb->rig->P, pb->sJtj.as<float>(), pb->sJtr.as<float>(), hd.factorScratch, pb->sDvec.as<float>(), pb->sRefState.as<int32_t>(),
+      pb->sErr.as<double>(), theta_dev, who, sp, s));
+  for (int round = 0; round < sp.refine; ++round) {
+    MMX_HIP(mmx::launchTreeRefine(
+        hd.sv.rig, hd.sv.pb, hd.sv.fd, theta_dev, pb->sTreeState.as<float>(), hd.genState, pb->sDvec.as<float>(), pb->sRhoVec.as<float>(), pb->sRefState.as<int32_t>(),
+        sp.lambda, sp.lambdaPer, s));
+    MMX_HIP(mmx::launchCholeskyFinishTiled(
+        hd.ds, pb->rig->P, hd.factorScratch, pb->sDvec.as<float>(), pb->sRhoVec.as<float>(), pb->sRefState.as<int32_t>(), pb->sErr.as<double>(),
+        theta_dev, who, sp, round, s));
+  }
+  return MMX_OK;
+}
+
+// TrustRegionQRT::doIteration (trust_region_qr.cpp:52-270) from the host: per pass, the instances whose damping changed factor
+// and solve, every instance with a step on the table decides (try it, or a Newton update of lambda first), the ready ones run
+// their trial.  At most ten trust steps of up to four solves each; the loop ends as soon as no instance is left in the
+// iteration (one 4-byte read-back per pass).
+int32_t trustRegionPasses(mmx_problem* pb, const HostDriven& hd, float* theta_dev, hipStream_t s) {
+  MMX_ZONE("TrustRegionQR: trust steps");
+  const mmx::StepParams& sp = hd.sp;
+  MMX_HIP(mmx::launchTrustBegin(sp.tr, hd.st, sp.lambdaPer, pb->B, s));
+  mmx::SolveStateDev masked = hd.st;
+  masked.done = sp.tr.mask;
+  for (int pass = 0; pass < 40; ++pass) {
+    MMX_TRY(treeLinearSolve(pb, hd, masked, theta_dev, s));
+    MMX_HIP(mmx::launchTrustDecide(hd.ds, hd.factorScratch, pb->sJtr.as<float>(), pb->sErr.as<double>(), hd.st, sp, s));
+    MMX_HIP(mmx::zeroAsync(sp.tr.active, sizeof(int32_t), s));
+    MMX_HIP(mmx::launchStepUpdate(pb->rigDev, hd.ds, theta_dev, pb->sJtr.as<float>(), pb->sErr.as<double>(), sp, s));
+    int32_t active = 0;
+    MMX_HIP(hipMemcpyAsync(&active, sp.tr.active, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MMX_HIP(hipStreamSynchronize(s));
+    if (active == 0) {
+      break;
+    }
+  }
+  MMX_HIP(mmx::launchTrustEnd(hd.st, sp, pb->sErr.as<double>(), pb->B, s));
+  return MMX_OK;
+}
+
+// The iteration loop (solver.cpp:89).  The parameter history is copied after every iteration, every element (rows past an
+// element's last iteration are zeroed by the caller's finalize kernel).
+int32_t iterateHostDriven(
+    mmx_problem* pb, const mmx_gn_options* o, const mmx::SolveStage& stage, HostDriven& hd, float* theta_dev, float* parameter_history, hipStream_t s) {
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
+  const bool trust = o->step_rule == MMX_STEP_TRUST_REGION;
+  const mmx::SolveStateDev& st = hd.st;
+  mmx::StepParams& sp = hd.sp;
+  for (int it = 0; it < o->max_iterations; ++it) {
+    sp.iteration = it;
+    MMX_ZONE("GaussNewtonSolverT::doIteration");
+    if (stage.treeRefine) {
+      {
+        MMX_ZONE("Get JtJ and JtR");
+        MMX_HIP(mmx::launchTreeNormalEquations(
+            hd.sv.rig, hd.sv.pb, hd.sv.fd, theta_dev, pb->sJtj.as<float>(), pb->sJtr.as<float>(), st.done, pb->sErr.as<double>(),
+            pb->sTreeState.as<float>(), sp.clk != nullptr ? sp.clk + 8 : nullptr, hd.genState, true, s));
+      }
+      MMX_ZONE("Dense gauss newton step");
+      MMX_TRY(trust ? trustRegionPasses(pb, hd, theta_dev, s) : treeLinearSolve(pb, hd, st, theta_dev, s));
+    } else {
+      {
+        MMX_ZONE("Get JtJ and JtR");
+        MMX_HIP(mmx::launchFkJacobian(
+            pb->rigDev, pb->dev, theta_dev, pb->sJac.as<float>(), pb->sRes.as<float>(), pb->sErr.as<double>(), nullptr, st.done, s, nullptr, nullptr, true));
+        MMX_HIP(mmx::launchNormalEquations(
+            hd.ds, pb->rig->P, pb->sJac.as<float>(), pb->sRes.as<float>(), pb->sJtj.as<float>(), pb->sJtr.as<float>(), st.done, stage.wide, s));
+      }
+      {
+        MMX_ZONE("Dense gauss newton step");
+        MMX_HIP(mmx::launchCholeskyStep(
+            hd.ds, pb->rig->P, pb->sJac.as<float>(), pb->sRes.as<float>(), pb->sJtj.as<float>(), pb->sJtr.as<float>(), pb->sErr.as<double>(),
+            theta_dev, st, sp, hd.factorScratch, s));
+      }
+    }
+    if (stage.deferred && !trust) {
+      MMX_ZONE("Line search");
+      MMX_HIP(mmx::launchStepUpdate(pb->rigDev, hd.ds, theta_dev, pb->sJtr.as<float>(), pb->sErr.as<double>(), sp, s));
+    }
+    if (parameter_history != nullptr) {
+      MMX_HIP(hipMemcpy2DAsync(
+          parameter_history + size_t(it) * P, size_t(o->max_iterations) * P * sizeof(float), theta_dev, P * sizeof(float), P * sizeof(float), B,
+          hipMemcpyDeviceToDevice, s));
+    }
+  }
+  return MMX_OK;
+}
+
+int32_t runHostDriven(mmx_problem* pb, const mmx_gn_options* o, const mmx::SolveStage& stage, float* theta_dev, const SolveOutputs& out, hipStream_t s) {
+  pb->lastRoute = stage.route;
+  HostDriven hd;
+  MMX_TRY(prepareHostDriven(pb, o, stage, theta_dev, out, s, hd));
+  MMX_TRY(iterateHostDriven(pb, o, stage, hd, theta_dev, out.parameterHistory, s));
+  if (out.parameterHistory != nullptr) {
+    MMX_HIP(mmx::launchParamHistoryFinalize(out.parameterHistory, hd.st.iterations, pb->B, o->max_iterations, pb->rig->P, s));
+  }
+  MMX_HIP(mmx::launchSolveFinalize(theta_dev, pb->sThetaInit.as<float>(), pb->rig->P, hd.st, pb->B, s, hd.sp.diagAcc));
+  if (hd.sp.clk != nullptr) {
+    long long h[32];
+    MMX_TRY(readPhaseClocks(hd.sp.clk, s, h));
+    static const char* names[16] = {"load H / fence", "factor (in-HBM: write-back + trailing)", "solve", "refine: w = r - J d", "refine: rho = J^T w", "refine: solve", "factor: panel load (in-HBM)", "factor: panel chain (in-HBM)",
+                                    "tree NE: load", "tree NE: A, B forward kinematics", "tree NE: C units + hand-over", "tree NE: D own sums",
+                                    "tree NE: D subtree sums", "tree NE: E slot tables", "tree NE: F, G tiles", "tree NE: G extras"};
+    fprintf(stderr, "[mmx phase clocks, choleskyStepKernel block 0, all iterations] n = %d\n", hd.ds.n);
+    printPhaseClocks(names, stage.treeRefine ? 16 : 8, 40, h, -1);
+  }
+  return MMX_OK;
+}
+
+// ---- a plan's stages, in order
+
+int32_t runPlan(mmx_problem* pb, const mmx_gn_options* o, const mmx::SolvePlan& plan, float* theta_dev, SolveOutputs out, hipStream_t s) {
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
+  int32_t rc = MMX_OK;
+  if (plan.numStages > 1) {
+    // MMX_PRECISION_AUTO: the later stages start from the initial parameters and run on the elements the stage before them
+    // marked.  Everything that can fail in them is settled before the first stage touches theta, status and the histories.
+    MMX_TRY(ensureF64Scratch(pb));
+    MMX_HIP(pb->sThetaAuto.ensure(B * P * sizeof(float)));
+    MMX_HIP(pb->sAutoMap.ensure(B * sizeof(int32_t)));
+    MMX_HIP(pb->sAutoCount.ensure(sizeof(int32_t)));
+    MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
+    MMX_HIP(hipMemcpyAsync(pb->sThetaAuto.p, theta_dev, B * P * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (out.status == nullptr) {
+      out.status = pb->sStatus.as<int32_t>();
+    }
+  }
+  int32_t* const map = pb->sAutoMap.as<int32_t>();
+  int32_t* const count = pb->sAutoCount.as<int32_t>();
+  for (int i = 0; i < plan.numStages && rc == MMX_OK; ++i) {
+    const mmx::SolveStage& stage = plan.stages[i];
+    const bool all = stage.select == mmx::SolveStageSelect::All;
+    if (stage.select == mmx::SolveStageSelect::SingleSuspects) {
+      // a solve without the estimate (explicit-Jacobian route, the wide route's host-driven trust region): the cue stays the damping floor
+      const int32_t mask = MMX_SOLVE_ERROR_MASK | MMX_SOLVE_PRECISION_SUSPECT | (pb->diagValid ? 0 : MMX_SOLVE_DAMPING_FLOORED);
+      MMX_HIP(mmx::launchSelectSuspect(out.status, pb->B, mask, map, count, s));
+    } else if (stage.select == mmx::SolveStageSelect::MixedSuspects) {
+      // the elements whose conjugate gradients ran into the step limit in the mixed stage (the single-precision factor is no
+      // preconditioner any more: cond x eps ~ 1 -- BASELINE configs[1] at lambda = 1e-5) or that failed there
+      MMX_HIP(mmx::launchSelectSuspect(out.status, pb->B, MMX_SOLVE_ERROR_MASK | MMX_SOLVE_PRECISION_SUSPECT, map, count, s, MMX_SOLVE_MIXED));
+    }
+    if (stage.kind == mmx::SolveStageKind::Mixed) {
+      rc = runMixed(pb, o, theta_dev, out, all ? mmx::MixSelect{nullptr, nullptr, nullptr} : mmx::MixSelect{map, count, pb->sThetaAuto.as<float>()}, s);
+    } else if (stage.kind == mmx::SolveStageKind::Double) {
+      // every workgroup reads its element's parameters before it writes them: in place on the caller's float array
+      rc = runDouble(pb, o, nullptr, out, all ? mmx::F64Select{nullptr, nullptr, theta_dev, theta_dev} : mmx::F64Select{map, count, pb->sThetaAuto.as<float>(), theta_dev}, s);
+    } else if (stage.route == MMX_ROUTE_WAVE) {
+      rc = runWave(pb, o, theta_dev, out, 0, s);
+    } else if (stage.route == MMX_ROUTE_FUSED) {
+      rc = runFused(pb, o, stage, theta_dev, out, s);
+    } else {
+      rc = runHostDriven(pb, o, stage, theta_dev, out, s);
+    }
+  }
+  return rc;
+}
+
+// mmx_solve and its variants with histories: mmx_gn_options::precision picks the single-precision routes, the mixed or the
+// double instantiation on float parameters, or (MMX_PRECISION_AUTO) one after the other on the elements the one before marked
+int32_t solveImpl(mmx_problem* pb, const mmx_gn_options* o, float* theta_dev, const SolveOutputs& out, void* stream) {
+  MMX_ZONE("mmx_solve (SolverT::solve)");
+  if (o != nullptr) {
+    if (const char* why = mmx::preHandleRefusal(*o, out.stepHistory != nullptr)) {
+      return fail(MMX_ERR_INVALID_ARGUMENT, why);
+    }
+  }
+  MMX_TRY(checkProblem(pb, true));
+  if (o == nullptr || theta_dev == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "options / theta is null");
+  }
+  const mmx::SolvePlan plan = mmx::planSolve(solveFacts(pb, out, o->precision, pb->tuning.route == MMX_ROUTE_WAVE), *o);
+  if (plan.code != MMX_OK) {
+    return fail(plan.code, plan.message);
+  }
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  return runPlan(pb, o, plan, theta_dev, out, static_cast<hipStream_t>(stream));
+}
+
+// The *_host entry points: theta (and the outputs asked for) staged through the problem's scratch around `solve`
+template <typename T, typename Solve>
+int32_t solveStaged(mmx_problem* pb, T* theta_host, double* final_error_host, int32_t* iterations_host, int32_t* status_host, Solve solve) {
+  MMX_TRY(checkProblem(pb, true));
+  if (theta_host == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "theta is null");
+  }
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  MMX_HIP(pb->sTheta.ensure(B * P * sizeof(T)));
+  MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
+  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
+  MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
+  MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(T), hipMemcpyHostToDevice));
+  MMX_TRY(solve(pb->sTheta.as<T>(), pb->sFinalErr.as<double>(), pb->sIters.as<int32_t>(), pb->sStatus.as<int32_t>()));
+  MMX_HIP(hipDeviceSynchronize());
+  MMX_HIP(hipMemcpy(theta_host, pb->sTheta.p, B * P * sizeof(T), hipMemcpyDeviceToHost));
+  if (final_error_host) {
+    MMX_HIP(hipMemcpy(final_error_host, pb->sFinalErr.p, B * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (iterations_host) {
+    MMX_HIP(hipMemcpy(iterations_host, pb->sIters.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  if (status_host) {
+    MMX_HIP(hipMemcpy(status_host, pb->sStatus.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return MMX_OK;
+}
+
 } // namespace
+} // extern "C++"
+
+int32_t mmx_solve(
+    mmx_problem* pb,
+    const mmx_gn_options* o,
+    float* theta_dev,
+    double* final_error,
+    int32_t* iterations,
+    int32_t* status,
+    double* error_history,
+    void* stream) {
+  return solveImpl(pb, o, theta_dev, SolveOutputs{final_error, iterations, status, error_history, nullptr, nullptr}, stream);
+}
+
+int32_t mmx_solve_with_history(
+    mmx_problem* pb,
+    const mmx_gn_options* o,
+    float* theta_dev,
+    double* final_error,
+    int32_t* iterations,
+    int32_t* status,
+    double* error_history,
+    float* parameter_history,
+    void* stream) {
+  return solveImpl(pb, o, theta_dev, SolveOutputs{final_error, iterations, status, error_history, parameter_history, nullptr}, stream);
+}
+
+int32_t mmx_solve_with_step_history(
+    mmx_problem* pb,
+    const mmx_gn_options* o,
+    float* theta_dev,
+    double* final_error,
+    int32_t* iterations,
+    int32_t* status,
+    double* error_history,
+    float* parameter_history,
+    double* step_history,
+    void* stream) {
+  return solveImpl(pb, o, theta_dev, SolveOutputs{final_error, iterations, status, error_history, parameter_history, step_history}, stream);
+}
 
 int32_t mmx_solve_f64(
     mmx_problem* pb,
@@ -2514,113 +2437,17 @@ int32_t mmx_solve_f64(
   if (theta_dev == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "options / theta is null");
   }
-  return solveF64Impl(pb, o, theta_dev, final_error, iterations, status, error_history, nullptr, mmx::F64Select{nullptr, nullptr, nullptr, nullptr}, stream);
-}
-
-// theta_dev: double [B][P] in / out, or null when `select` carries float arrays (MMX_PRECISION_F64 / AUTO of mmx_solve)
-// What the double kernel needs before it can run on this problem: its LDS budget and, in the scratch form, the problem's global
-// scratch for J and H.  solveF64Impl calls it first; MMX_PRECISION_AUTO calls it before its single-precision pass, so that a
-// refusal or an allocation failure of the later stage leaves the caller's theta / status / histories untouched.
-static int32_t preflightF64(mmx_problem* pb) {
-  const size_t B = size_t(pb->B), n = size_t(pb->solveN), M = size_t(pb->dev.rowsJoint);
-  const int genRowsF64 = pb->dev.rowsJoint - 3 * pb->U;
-  MMX_HIP(hipSetDevice(pb->rig->device));
-  if (!mmx::solveF64IsResident(pb->rig->J, pb->rig->P, pb->U, pb->solveN, pb->dev.G + pb->dev.NE, genRowsF64)) {
-    if (mmx::solveF64LdsBytes(pb->rig->J, pb->rig->P, pb->U, pb->solveN, pb->dev.G + pb->dev.NE, genRowsF64) > 160 * 1024) {
-      return fail(MMX_ERR_UNSUPPORTED, "mmx_solve_f64: rig beyond the kernel's LDS budget");
-    }
-    MMX_HIP(pb->sJacF64.ensure(std::max<size_t>(B * n * M, 1) * sizeof(double)));
-    MMX_HIP(pb->sHessF64.ensure(std::max<size_t>(B * n * n, 1) * sizeof(double)));
-  }
-  return MMX_OK;
-}
-
-static int32_t solveF64Impl(
-    mmx_problem* pb,
-    const mmx_gn_options* o,
-    double* theta_dev,
-    double* final_error,
-    int32_t* iterations,
-    int32_t* status,
-    double* error_history,
-    double* step_history,
-    const mmx::F64Select& select,
-    void* stream) {
-  MMX_ZONE("mmx_solve_f64 (SolverT<double>::solve)");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  if (o == nullptr || (theta_dev == nullptr && select.thetaInit == nullptr)) {
+  MMX_TRY(checkProblem(pb, true));
+  if (o == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "options / theta is null");
   }
-  if (o->max_iterations < 0 || o->min_iterations < 0) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "iteration counts must be >= 0");
+  const SolveOutputs out{final_error, iterations, status, error_history, nullptr, nullptr};
+  const mmx::SolvePlan plan = mmx::planSolveF64(solveFacts(pb, out, MMX_PRECISION_F64, false), *o);
+  if (plan.code != MMX_OK) {
+    return fail(plan.code, plan.message);
   }
-  if (o->step_rule != MMX_STEP_GN_FIXED_LAMBDA && o->step_rule != MMX_STEP_LM_SCHEDULE && o->step_rule != MMX_STEP_TRUST_REGION) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "unknown step_rule");
-  }
-  if (o->do_line_search != MMX_LINE_SEARCH_NONE && o->do_line_search != MMX_LINE_SEARCH_GAUSS_NEWTON &&
-      o->do_line_search != MMX_LINE_SEARCH_DIRECTIONAL) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "unknown do_line_search rule");
-  }
-  const size_t B = size_t(pb->B), n = size_t(pb->solveN), M = size_t(pb->dev.rowsJoint);
-  const int genRowsF64 = pb->dev.rowsJoint - 3 * pb->U;
   MMX_HIP(hipSetDevice(pb->rig->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool residentF64 = mmx::solveF64IsResident(pb->rig->J, pb->rig->P, pb->U, pb->solveN, pb->dev.G + pb->dev.NE, genRowsF64);
-  rc = preflightF64(pb); // (the scratch form: dense J and H of every element in a global scratch of the problem)
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  const bool trustF64 = o->step_rule == MMX_STEP_TRUST_REGION;
-  if (trustF64) {
-    MMX_HIP(pb->sHess2F64.ensure(std::max<size_t>(B * n * n, 1) * sizeof(double)));
-  }
-  MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
-  mmx::SolveStateDev st{};
-  st.iterations = iterations != nullptr ? iterations : pb->sIters.as<int32_t>();
-  st.status = status != nullptr ? status : pb->sStatus.as<int32_t>();
-  st.finalError = final_error != nullptr ? final_error : pb->sFinalErr.as<double>();
-  st.errorHistory = error_history;
-  st.stepHistory = step_history;
-  const bool escalation = select.map != nullptr; // (the single-precision solve's outputs stay for the other elements)
-  if (error_history != nullptr && o->max_iterations > 0 && !escalation) {
-    MMX_HIP(mmx::zeroAsync(error_history, B * size_t(o->max_iterations) * sizeof(double), s));
-  }
-  if (step_history != nullptr && o->max_iterations > 0 && !escalation) {
-    MMX_HIP(mmx::zeroAsync(step_history, B * size_t(o->max_iterations) * 2 * sizeof(double), s));
-  }
-  mmx::FusedParams fp{};
-  fp.lambda = o->regularization;
-  fp.threshold = o->threshold;
-  fp.minIterations = o->min_iterations;
-  fp.maxIterations = o->max_iterations;
-  fp.doLineSearch = o->do_line_search;
-  fp.stepRule = o->step_rule;
-  fp.lmLambdaMin = o->lm_lambda_min;
-  fp.lmLambdaMax = o->lm_lambda_max;
-  fp.lmUp = o->lm_up;
-  fp.lmDown = o->lm_down;
-  fp.trustRadius = o->trust_region_radius > 0.f ? o->trust_region_radius : 1.f;
-  mmx::F64AssemblyList alist{nullptr, nullptr, nullptr, 0};
-  if (residentF64 && pb->dev.instPosParent == nullptr && pb->dev.instOriParent == nullptr && pb->rig->J < 4096 && pb->solveN <= 4096) {
-    const int32_t uc = mmx::solveF64ResidentChunkRows(pb->rig->J, pb->rig->P, pb->U, pb->solveN, pb->dev.G + pb->dev.NE, genRowsF64) / 3;
-    if (uc > 0 && uc <= 64) {
-      if (pb->f64ListUnitsPerChunk != uc) {
-        rc = buildF64AssemblyList(pb, uc);
-        if (rc != MMX_OK) {
-          return rc;
-        }
-      }
-      alist = mmx::F64AssemblyList{pb->dF64Groups.as<uint2>(), pb->dF64Extra.as<int32_t>(), pb->dF64ChunkStart.as<int32_t>(), uc};
-    }
-  }
-  MMX_HIP(mmx::launchSolveF64(
-      pb->rigDev, pb->dev, pb->dSolveListF64.as<int32_t>(), pb->solveN, theta_dev, st, fp, pb->sJacF64.as<double>(), pb->sHessF64.as<double>(), trustF64 ? pb->sHess2F64.as<double>() : nullptr, s, alist, select));
-  return MMX_OK;
+  return runDouble(pb, o, theta_dev, out, mmx::F64Select{nullptr, nullptr, nullptr, nullptr}, static_cast<hipStream_t>(stream));
 }
 
 int32_t mmx_debug_fused_normal_equations(
@@ -2631,10 +2458,7 @@ int32_t mmx_debug_fused_normal_equations(
     int32_t* solve_list_host,
     int32_t* num_solved,
     void* stream) {
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, true));
   const int n = pb->fdev.n;
   if (num_solved != nullptr) {
     *num_solved = n;
@@ -2679,36 +2503,9 @@ int32_t mmx_solve_host(
     int32_t* iterations_host,
     int32_t* status_host) {
   MMX_ZONE("mmx_solve_host");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  if (theta_host == nullptr) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "theta is null");
-  }
-  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
-  MMX_HIP(hipSetDevice(pb->rig->device));
-  MMX_HIP(pb->sTheta.ensure(B * P * sizeof(float)));
-  MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
-  MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(float), hipMemcpyHostToDevice));
-  rc = mmx_solve(pb, o, pb->sTheta.as<float>(), pb->sFinalErr.as<double>(), pb->sIters.as<int32_t>(), pb->sStatus.as<int32_t>(), nullptr, nullptr);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  MMX_HIP(hipDeviceSynchronize());
-  MMX_HIP(hipMemcpy(theta_host, pb->sTheta.p, B * P * sizeof(float), hipMemcpyDeviceToHost));
-  if (final_error_host) {
-    MMX_HIP(hipMemcpy(final_error_host, pb->sFinalErr.p, B * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  if (iterations_host) {
-    MMX_HIP(hipMemcpy(iterations_host, pb->sIters.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  if (status_host) {
-    MMX_HIP(hipMemcpy(status_host, pb->sStatus.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  return MMX_OK;
+  return solveStaged<float>(pb, theta_host, final_error_host, iterations_host, status_host, [&](float* theta, double* err, int32_t* iters, int32_t* status) {
+    return mmx_solve(pb, o, theta, err, iters, status, nullptr, nullptr);
+  });
 }
 
 // Frame sequences on the one-wavefront route: the batch is num_frames x S instances, frame-major, and a wave owns a sequence --
@@ -2726,63 +2523,17 @@ int32_t mmx_solve_frames(
     float* parameter_history,
     void* stream) {
   MMX_ZONE("mmx_solve_frames (SolverT::solve per frame, warm-started along the sequence)");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, true));
   if (o == nullptr || theta_dev == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "options / theta is null");
   }
-  if (num_frames < 1 || pb->B % num_frames != 0) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_solve_frames: num_frames must be >= 1 and divide the problem's batch (num_frames x sequences instances, frame-major)");
+  const SolveOutputs out{final_error, iterations, status, error_history, parameter_history, nullptr};
+  const mmx::SolvePlan plan = mmx::planSolveFrames(solveFacts(pb, out, MMX_PRECISION_F32, true), *o, pb->B, num_frames);
+  if (plan.code != MMX_OK) {
+    return fail(plan.code, plan.message);
   }
-  if (o->max_iterations < 0 || o->min_iterations < 0) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "iteration counts must be >= 0");
-  }
-  if (o->do_line_search != MMX_LINE_SEARCH_NONE && o->do_line_search != MMX_LINE_SEARCH_GAUSS_NEWTON &&
-      o->do_line_search != MMX_LINE_SEARCH_DIRECTIONAL) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "unknown do_line_search rule");
-  }
-  if (o->precision != MMX_PRECISION_F32) {
-    return fail(MMX_ERR_UNSUPPORTED, "mmx_solve_frames runs on MMX_ROUTE_WAVE: only MMX_PRECISION_F32 (not F64 / AUTO / MIXED)");
-  }
-  if (pb->tuning.route != MMX_ROUTE_AUTO && pb->tuning.route != MMX_ROUTE_WAVE) {
-    return fail(MMX_ERR_UNSUPPORTED, "mmx_solve_frames runs on the one-wavefront route only: the handle's route is pinned to another (MMX_ROUTE_AUTO or MMX_ROUTE_WAVE)");
-  }
-  if (const char* why = waveRefusal(pb, o, true)) {
-    return fail(MMX_ERR_UNSUPPORTED, why);
-  }
-  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
   MMX_HIP(hipSetDevice(pb->rig->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  pb->lastRoute = MMX_ROUTE_WAVE;
-  pb->diagValid = false; // (no precision estimate on this route)
-  MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
-  mmx::SolveStateDev wst{};
-  wst.iterations = iterations != nullptr ? iterations : pb->sIters.as<int32_t>();
-  wst.status = status != nullptr ? status : pb->sStatus.as<int32_t>();
-  wst.finalError = final_error != nullptr ? final_error : pb->sFinalErr.as<double>();
-  wst.errorHistory = error_history;
-  wst.paramHistory = parameter_history;
-  if (error_history != nullptr && o->max_iterations > 0) {
-    MMX_HIP(mmx::zeroAsync(error_history, B * size_t(o->max_iterations) * sizeof(double), s));
-  }
-  if (parameter_history != nullptr && o->max_iterations > 0) {
-    MMX_HIP(mmx::zeroAsync(parameter_history, B * size_t(o->max_iterations) * P * sizeof(float), s));
-  }
-  mmx::FusedParams wp{};
-  wp.lambda = o->regularization;
-  wp.threshold = o->threshold;
-  wp.minIterations = o->min_iterations;
-  wp.maxIterations = o->max_iterations;
-  wp.refine = refineSteps(pb);
-  wp.doLineSearch = o->do_line_search;
-  wp.stepRule = o->step_rule;
-  const SolveView sv = solveView(pb);
-  MMX_HIP(mmx::launchWaveFrames(sv.rig, sv.pb, sv.fd, theta_dev, wst, wp, num_frames, s));
-  return MMX_OK;
+  return runWave(pb, o, theta_dev, out, num_frames, static_cast<hipStream_t>(stream));
 }
 
 int32_t mmx_solve_frames_host(
@@ -2794,36 +2545,9 @@ int32_t mmx_solve_frames_host(
     int32_t* iterations_host,
     int32_t* status_host) {
   MMX_ZONE("mmx_solve_frames_host");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  if (theta_host == nullptr) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "theta is null");
-  }
-  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
-  MMX_HIP(hipSetDevice(pb->rig->device));
-  MMX_HIP(pb->sTheta.ensure(B * P * sizeof(float)));
-  MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
-  MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(float), hipMemcpyHostToDevice));
-  rc = mmx_solve_frames(pb, o, num_frames, pb->sTheta.as<float>(), pb->sFinalErr.as<double>(), pb->sIters.as<int32_t>(), pb->sStatus.as<int32_t>(), nullptr, nullptr, nullptr);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  MMX_HIP(hipDeviceSynchronize());
-  MMX_HIP(hipMemcpy(theta_host, pb->sTheta.p, B * P * sizeof(float), hipMemcpyDeviceToHost));
-  if (final_error_host) {
-    MMX_HIP(hipMemcpy(final_error_host, pb->sFinalErr.p, B * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  if (iterations_host) {
-    MMX_HIP(hipMemcpy(iterations_host, pb->sIters.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  if (status_host) {
-    MMX_HIP(hipMemcpy(status_host, pb->sStatus.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  return MMX_OK;
+  return solveStaged<float>(pb, theta_host, final_error_host, iterations_host, status_host, [&](float* theta, double* err, int32_t* iters, int32_t* status) {
+    return mmx_solve_frames(pb, o, num_frames, theta, err, iters, status, nullptr, nullptr, nullptr);
+  });
 }
 
 int32_t mmx_solve_f64_host(
@@ -2834,44 +2558,14 @@ int32_t mmx_solve_f64_host(
     int32_t* iterations_host,
     int32_t* status_host) {
   MMX_ZONE("mmx_solve_f64_host");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  if (theta_host == nullptr) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "theta is null");
-  }
-  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
-  MMX_HIP(hipSetDevice(pb->rig->device));
-  MMX_HIP(pb->sTheta.ensure(B * P * sizeof(double)));
-  MMX_HIP(pb->sIters.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sStatus.ensure(B * sizeof(int32_t)));
-  MMX_HIP(pb->sFinalErr.ensure(B * sizeof(double)));
-  MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(double), hipMemcpyHostToDevice));
-  rc = mmx_solve_f64(pb, o, pb->sTheta.as<double>(), pb->sFinalErr.as<double>(), pb->sIters.as<int32_t>(), pb->sStatus.as<int32_t>(), nullptr, nullptr);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  MMX_HIP(hipDeviceSynchronize());
-  MMX_HIP(hipMemcpy(theta_host, pb->sTheta.p, B * P * sizeof(double), hipMemcpyDeviceToHost));
-  if (final_error_host) {
-    MMX_HIP(hipMemcpy(final_error_host, pb->sFinalErr.p, B * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  if (iterations_host) {
-    MMX_HIP(hipMemcpy(iterations_host, pb->sIters.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  if (status_host) {
-    MMX_HIP(hipMemcpy(status_host, pb->sStatus.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  return MMX_OK;
+  return solveStaged<double>(pb, theta_host, final_error_host, iterations_host, status_host, [&](double* theta, double* err, int32_t* iters, int32_t* status) {
+    return mmx_solve_f64(pb, o, theta, err, iters, status, nullptr, nullptr);
+  });
 }
 
 int32_t mmx_eval_skeleton_state_host(mmx_problem* pb, const float* theta_host, float* state_host) {
   MMX_ZONE("mmx_eval_skeleton_state_host");
-  int32_t rc = checkProblem(pb, false);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, false));
   if (theta_host == nullptr || state_host == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "theta / state is null");
   }
@@ -2880,10 +2574,7 @@ int32_t mmx_eval_skeleton_state_host(mmx_problem* pb, const float* theta_host, f
   MMX_HIP(pb->sTheta.ensure(B * P * sizeof(float)));
   MMX_HIP(pb->sRes.ensure(B * J * 8 * sizeof(float)));
   MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(float), hipMemcpyHostToDevice));
-  rc = mmx_eval_skeleton_state(pb, pb->sTheta.as<float>(), pb->sRes.as<float>(), nullptr);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(mmx_eval_skeleton_state(pb, pb->sTheta.as<float>(), pb->sRes.as<float>(), nullptr));
   MMX_HIP(hipDeviceSynchronize());
   MMX_HIP(hipMemcpy(state_host, pb->sRes.p, B * J * 8 * sizeof(float), hipMemcpyDeviceToHost));
   return MMX_OK;
@@ -2897,10 +2588,7 @@ int32_t mmx_eval_jacobian_host(
     double* err_host,
     int32_t layout) {
   MMX_ZONE("mmx_eval_jacobian_host");
-  int32_t rc = checkProblem(pb, true);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(checkProblem(pb, true));
   if (theta_host == nullptr) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "theta is null");
   }
@@ -2911,10 +2599,7 @@ int32_t mmx_eval_jacobian_host(
   MMX_HIP(pb->sRes.ensure(B * std::max<size_t>(M, 1) * sizeof(float)));
   MMX_HIP(pb->sErr.ensure(B * sizeof(double)));
   MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(float), hipMemcpyHostToDevice));
-  rc = mmx_eval_jacobian(pb, pb->sTheta.as<float>(), pb->sJac.as<float>(), pb->sRes.as<float>(), pb->sErr.as<double>(), layout, nullptr);
-  if (rc != MMX_OK) {
-    return rc;
-  }
+  MMX_TRY(mmx_eval_jacobian(pb, pb->sTheta.as<float>(), pb->sJac.as<float>(), pb->sRes.as<float>(), pb->sErr.as<double>(), layout, nullptr));
   MMX_HIP(hipDeviceSynchronize());
   if (jac_host) {
     MMX_HIP(hipMemcpy(jac_host, pb->sJac.p, B * M * P * sizeof(float), hipMemcpyDeviceToHost));

@@ -129,7 +129,7 @@ def test_build_recipe_flags_per_translation_unit():
     for g in (0, 1, 2, 3, 5, 6):
         assert mbuild._extra_flags("mmx_fused.hip", g) == solve
     assert mbuild._extra_flags("mmx_f64.hip", None) == solve
-    for src, g in (("mmx_fused.hip", 4), ("mmx_kernels.hip", None), ("mmx_capi.hip", None), ("mmx_comm.hip", None), ("mmx_host_tables.cpp", None)):
+    for src, g in (("mmx_fused.hip", 4), ("mmx_kernels.hip", None), ("mmx_capi.hip", None), ("mmx_comm.hip", None), ("mmx_host_tables.cpp", None), ("mmx_solve_plan.cpp", None)):
         assert mbuild._extra_flags(src, g) == []
     text = open(os.path.join(os.path.dirname(mbuild.__file__), "csrc", "mmx_fused.hip")).read()
     groups = {int(g) for g in re.findall(r"MMX_FUSED_GROUP == (\d+)", text)} - {8, 9}  # (8, 9: the one-instantiation compile probes)
