@@ -838,6 +838,37 @@ int32_t mmx_solve_frames_host(
     int32_t* status_host);
 
 /*
+ * The error and the gradient of every instance WITHOUT a Jacobian: SkeletonSolverFunctionT::getGradient
+ * (error_function_helpers.cpp:220) and getError in O(joints + constraints) per instance, through the skeleton tree (the
+ * adjoint pass the wide route refines with), where mmx_eval_jacobian writes M x P floats per instance first.  Added without
+ * an ABI bump (no struct grows): a library that predates the functions lacks the symbols -- that is the feature probe.
+ *   meaning     with J and r as mmx_eval_jacobian returns them for the handle's current state (constraints, enabled mask,
+ *               per-instance rig, losses, per-element function weights):
+ *                 grad_dev [B][P]  grad[b][p] = 2 sum_i J[b][i][p] r[b][i].  All P entries of every row are written; the
+ *                                  entries of disabled parameters and of structurally zero columns are exact zeros.
+ *                 err_dev  [B]     the error mmx_eval_jacobian reports (under a robust loss the loss value, not |r|^2).
+ *               The forward kinematics is the solve kernels' (pointer-jumping rounds in double), so err is the error a
+ *               solve reports at theta; mmx_eval_jacobian keeps single-precision rounds, the two agree to rounding.
+ *   forms       grad_dev == NULL: the error only (no moments, no tree sums); err_dev == NULL: the gradient only.  An
+ *               output has the same bits whichever form produced it.  Both NULL: MMX_ERR_INVALID_ARGUMENT.
+ *   scope       position and orientation blocks with every GeneralizedLoss the solves take; constraint, block and
+ *               per-element function weights (columns 0-3); the parameter-space rows (every MMX_LIMIT_* type but the
+ *               ellipsoid, the model-parameter prior); the enabled mask; per-instance offsets and pre-rotations.
+ *   refusals    MMX_ERR_UNSUPPORTED with a message that names the condition, before any output is touched, the first
+ *               that applies in this order: further joint-constraint blocks; ellipsoid limits; per-instance constraint
+ *               parents; no position / orientation constraint or no solved parameter; tables beyond the kernel's LDS
+ *               budget (160 KB).  There is no fallback through the Jacobian: those problems stay with mmx_eval_jacobian.
+ *   determinism a row of the result depends on that instance's inputs only -- not on the batch size, the instance's
+ *               position in the batch, or the run (no floating-point atomics; every entry is summed by one thread in a
+ *               fixed order).
+ * One kernel is enqueued on `stream` and the call returns (no memset node, no stream wait, no host read): after one
+ * warm-up call it can be captured into a HIP graph like the solves.  The _host form copies in, runs, copies out and
+ * synchronises like the other host wrappers.
+ */
+int32_t mmx_eval_gradient(mmx_problem* problem, const float* theta_dev, float* grad_dev, double* err_dev, void* stream);
+int32_t mmx_eval_gradient_host(mmx_problem* problem, const float* theta_host, float* grad_host, double* err_host);
+
+/*
  * Numerical diagnostics of the LAST single-precision solve on this handle (one-launch and wide routes;
  * MMX_ERR_UNSUPPORTED after a solve on the explicit-Jacobian route or before the first solve): diag_dev [B][4] floats
  *   [0] the precision estimate MMX_SOLVE_PRECISION_SUSPECT is decided on (relative to |theta|)

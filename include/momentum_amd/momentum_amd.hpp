@@ -646,6 +646,19 @@ class BatchedSkeletonSolverFunction {
     error.resize(batch_);
     check(mmx_eval_jacobian_host(handle_.get(), parameters.data(), jacobian.data(), residual.data(), error.data(), MMX_LAYOUT_COL_MAJOR));
   }
+  // SolverFunctionT::getGradient for every element without a Jacobian (mmx_eval_gradient): gradient P per element (2 J^T r,
+  // exact zeros for disabled parameters), and the error.  Throws for problems outside the matrix-free kernel's scope (further
+  // joint error functions, ellipsoid limits, per-element constraint parents): there is no fallback through getJacobian.
+  void getGradient(const std::vector<float>& parameters, std::vector<float>& gradient, std::vector<double>& error) {
+    sync();
+    const size_t P = getNumParameters();
+    if (parameters.size() != batch_ * P) {
+      throw std::runtime_error("momentum_amd: parameters.size() != batch * numParameters"); // solver.cpp:77
+    }
+    gradient.resize(batch_ * P);
+    error.resize(batch_);
+    check(mmx_eval_gradient_host(handle_.get(), parameters.data(), gradient.data(), error.data()));
+  }
   mmx_problem* handle() const {
     return handle_.get();
   }
@@ -981,6 +994,12 @@ class SkeletonSolverFunction : public BatchedSkeletonSolverFunction {
   double getJacobian(const std::vector<float>& parameters, std::vector<float>& jacobian, std::vector<float>& residual) {
     std::vector<double> e;
     BatchedSkeletonSolverFunction::getJacobian(parameters, jacobian, residual, e);
+    return e.at(0);
+  }
+  // SolverFunctionT::getGradient: gradient [P] without a Jacobian (mmx_eval_gradient), returns the error
+  double getGradient(const std::vector<float>& parameters, std::vector<float>& gradient) {
+    std::vector<double> e;
+    BatchedSkeletonSolverFunction::getGradient(parameters, gradient, e);
     return e.at(0);
   }
   // SolverFunctionT::getError: the same evaluation without keeping the Jacobian

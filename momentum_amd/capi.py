@@ -30,6 +30,7 @@ SYMBOLS = [
     "mmx_problem_set_enabled", "mmx_problem_set_constraints", "mmx_problem_set_constraints_sized", "mmx_problem_set_instance_rig", "mmx_problem_set_instance_parents", "mmx_eval_jacobian", "mmx_eval_jacobian_timed", "mmx_debug_store_pattern",
     "mmx_eval_skeleton_state", "mmx_eval_normal_equations", "mmx_solve", "mmx_solve_with_history", "mmx_solve_with_step_history", "mmx_problem_solve_diagnostics", "mmx_solve_f64", "mmx_solve_f64_host", "mmx_solve_host",
     "mmx_solve_frames", "mmx_solve_frames_host",
+    "mmx_eval_gradient", "mmx_eval_gradient_host",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
     "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
@@ -93,6 +94,8 @@ def lib() -> C.CDLL:
     L.mmx_solve_f64_host.argtypes = [vp, C.POINTER(GnOptions), vp, vp, vp, vp]
     L.mmx_solve_frames.argtypes = [vp, C.POINTER(GnOptions), i32, vp, vp, vp, vp, vp, vp, vp]
     L.mmx_solve_frames_host.argtypes = [vp, C.POINTER(GnOptions), i32, vp, vp, vp, vp]
+    L.mmx_eval_gradient.argtypes = [vp, vp, vp, vp, vp]
+    L.mmx_eval_gradient_host.argtypes = [vp, vp, vp, vp]
     L.mmx_eval_jacobian_host.argtypes = [vp, vp, vp, vp, vp, i32]
     L.mmx_eval_skeleton_state_host.argtypes = [vp, vp, vp]
     L.mmx_debug_tree_normal_equations.argtypes = [vp, vp, vp, vp, vp]
@@ -473,6 +476,26 @@ class Problem:
         layout = _abi.MMX_LAYOUT_ROW_MAJOR if row_major else _abi.MMX_LAYOUT_COL_MAJOR
         _check(lib().mmx_eval_jacobian(self._h, _dev(theta), _dev(jac), _dev(res), _dev(err), layout, _stream_ptr()))
         return jac, res, err
+
+    # -- error and gradient without a Jacobian (mmx_eval_gradient)
+    def eval_gradient(self, theta, grad=None, err=None, want_grad: bool = True, want_err: bool = True):
+        """Returns (grad [B,P] float32 = 2 J^T r with exact zeros for disabled / structurally zero columns, err [B] float64);
+        an output that is not wanted (want_grad / want_err False and no buffer given) is None and is not computed.  Raises
+        MmxError (MMX_ERR_UNSUPPORTED, no fallback) for problems outside the matrix-free kernel's scope: further joint blocks,
+        ellipsoid limits, per-instance constraint parents."""
+        import torch
+
+        theta = self._theta(theta)
+        if grad is None and want_grad:
+            grad = torch.empty((self.B, self.P), dtype=torch.float32, device=self.device)
+        if err is None and want_err:
+            err = torch.empty((self.B,), dtype=torch.float64, device=self.device)
+        if grad is not None:
+            assert grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous() and tuple(grad.shape) == (self.B, self.P), grad.shape
+        if err is not None:
+            assert err.is_cuda and err.dtype == torch.float64 and err.is_contiguous() and tuple(err.shape) == (self.B,), err.shape
+        _check(lib().mmx_eval_gradient(self._h, _dev(theta), _dev(grad), _dev(err), _stream_ptr()))
+        return grad, err
 
     def eval_jacobian_kernel_ms(self, theta, jac, res, err=None) -> float:
         """Duration (ms) of the J-assembly kernel itself: events attached to its dispatch packet

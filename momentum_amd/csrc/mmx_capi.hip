@@ -2563,6 +2563,53 @@ int32_t mmx_solve_f64_host(
   });
 }
 
+int32_t mmx_eval_gradient(mmx_problem* pb, const float* theta_dev, float* grad_dev, double* err_dev, void* stream) {
+  MMX_ZONE("mmx_eval_gradient (getGradient without a Jacobian)");
+  MMX_TRY(checkProblem(pb, true));
+  if (theta_dev == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "theta is null");
+  }
+  if (grad_dev == nullptr && err_dev == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_eval_gradient: grad and err are both null (ask for at least one output)");
+  }
+  // the scope decision is host code of its own (mmx_solve_plan.cpp): a refusal comes before any output is touched
+  mmx::SolveFacts facts; // (the facts gradientRefusal reads; the solves' budgets stay at their defaults)
+  facts.numBlocks = pb->dev.numBlocks, facts.G = pb->dev.G, facts.NE = pb->dev.NE;
+  facts.instanceParents = pb->dev.instPosParent != nullptr || pb->dev.instOriParent != nullptr;
+  facts.U = pb->U, facts.n = pb->fdev.n;
+  facts.gradientLdsBytes = mmx::gradientLdsBytes(pb->rig->J, pb->rig->P, pb->U);
+  if (const char* why = mmx::gradientRefusal(facts)) {
+    return fail(MMX_ERR_UNSUPPORTED, why);
+  }
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  const SolveView sv = solveView(pb);
+  MMX_HIP(mmx::launchEvalGradient(sv.rig, sv.pb, sv.fd, theta_dev, grad_dev, err_dev, static_cast<hipStream_t>(stream)));
+  return MMX_OK;
+}
+
+int32_t mmx_eval_gradient_host(mmx_problem* pb, const float* theta_host, float* grad_host, double* err_host) {
+  MMX_ZONE("mmx_eval_gradient_host");
+  MMX_TRY(checkProblem(pb, true));
+  if (theta_host == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "theta is null");
+  }
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  MMX_HIP(pb->sTheta.ensure(B * P * sizeof(float)));
+  MMX_HIP(pb->sJtr.ensure(B * P * sizeof(float)));
+  MMX_HIP(pb->sErr.ensure(B * sizeof(double)));
+  MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(float), hipMemcpyHostToDevice));
+  MMX_TRY(mmx_eval_gradient(pb, pb->sTheta.as<float>(), grad_host != nullptr ? pb->sJtr.as<float>() : nullptr, err_host != nullptr ? pb->sErr.as<double>() : nullptr, nullptr));
+  MMX_HIP(hipDeviceSynchronize());
+  if (grad_host) {
+    MMX_HIP(hipMemcpy(grad_host, pb->sJtr.p, B * P * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  if (err_host) {
+    MMX_HIP(hipMemcpy(err_host, pb->sErr.p, B * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return MMX_OK;
+}
+
 int32_t mmx_eval_skeleton_state_host(mmx_problem* pb, const float* theta_host, float* state_host) {
   MMX_ZONE("mmx_eval_skeleton_state_host");
   MMX_TRY(checkProblem(pb, false));

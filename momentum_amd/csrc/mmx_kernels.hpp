@@ -214,6 +214,12 @@ hipError_t launchTreeRefine(
     float lambda,
     const float* lambdaPer,
     hipStream_t stream);
+// mmx_eval_gradient (mmx_gradient.hip): err[b] = the error, grad[b][p] = 2 (J^T r)_p through the tree, no Jacobian; one
+// 256-thread workgroup per instance, one kernel node.  Position / orientation blocks with any loss and the parameter-space
+// rows; no further joint blocks, ellipsoid limits or per-instance parents (mmx_solve_plan.hpp gradientRefusal).  grad or err
+// may be null (not both): without grad the moments, tree sums and gather are skipped.
+size_t gradientLdsBytes(int J, int P, int U);
+hipError_t launchEvalGradient(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, const float* theta, float* grad, double* err, hipStream_t stream);
 int fusedBlocksFor(int n); // number of 16-wide blocks the fused kernel is instantiated for, or -1
 hipError_t launchFusedSolve(
     const RigDev& rig,

@@ -159,6 +159,25 @@ const char* waveRefusal(const SolveFacts& f, const mmx_gn_options& o, bool frame
   return nullptr;
 }
 
+const char* gradientRefusal(const SolveFacts& f) {
+  if (f.numBlocks > 0 || f.G > 0) {
+    return "mmx_eval_gradient: further joint-constraint blocks are outside the matrix-free kernel (mmx_eval_jacobian takes them)";
+  }
+  if (f.NE > 0) {
+    return "mmx_eval_gradient: ellipsoid limits are outside the matrix-free kernel (mmx_eval_jacobian takes them)";
+  }
+  if (f.instanceParents) {
+    return "mmx_eval_gradient: per-instance constraint parents are outside the matrix-free kernel (mmx_eval_jacobian takes them)";
+  }
+  if (f.U <= 0 || f.n <= 0) {
+    return "mmx_eval_gradient: no position / orientation constraint, or no solved parameter";
+  }
+  if (f.gradientLdsBytes > kPlanLdsBudget - 64) {
+    return "mmx_eval_gradient: the rig's tables do not fit the kernel's LDS budget (160 KB)";
+  }
+  return nullptr;
+}
+
 SolvePlan planSolveF64(const SolveFacts& f, const mmx_gn_options& o) {
   if (const char* why = optionsRefusal(o, true)) {
     return refuse(MMX_ERR_INVALID_ARGUMENT, why);

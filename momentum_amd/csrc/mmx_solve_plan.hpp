@@ -33,6 +33,7 @@ struct SolveFacts {
   bool instanceParents = false; // per-instance constraint parents are set
   // the optional outputs the caller passed
   bool parameterHistory = false, stepHistory = false;
+  size_t gradientLdsBytes = 0; // mmx_eval_gradient's kernel (gradientRefusal reads it; the solve plans do not)
 };
 
 enum class SolveStageKind : int32_t { Single, Mixed, Double };
@@ -66,6 +67,8 @@ const char* preHandleRefusal(const mmx_gn_options& o, bool stepHistory);
 const char* optionsRefusal(const mmx_gn_options& o, bool checkStepRule);
 // MMX_ROUTE_WAVE's scope (table in include/mmx.h): null when the route takes the problem with these options
 const char* waveRefusal(const SolveFacts& f, const mmx_gn_options& o, bool frames);
+// mmx_eval_gradient's scope (include/mmx.h), in its documented order: null when the matrix-free kernel takes the problem
+const char* gradientRefusal(const SolveFacts& f);
 
 SolvePlan planSolve(const SolveFacts& f, const mmx_gn_options& o); // mmx_solve, mmx_solve_with_history, ..._with_step_history
 SolvePlan planSolveF64(const SolveFacts& f, const mmx_gn_options& o); // mmx_solve_f64

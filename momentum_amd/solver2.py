@@ -504,10 +504,15 @@ class SkeletonSolverFunction(SolverFunction):
             raise RuntimeError(f"Expected parameters to be of size {P}")
         return mp.ndim == 1, mp.reshape(-1, P)
 
-    def get_error(self, model_parameters):
+    def get_error(self, model_parameters, matrix_free: bool = False):
+        """matrix_free: through mmx_eval_gradient's error-only form (no Jacobian is written; MmxError for a problem outside
+        its scope, never a fallback) instead of the Jacobian path, which stays the default."""
         single, mp = self._params(model_parameters)
         pb, torch = self.lower(mp.shape[0])
-        _, _, err = pb.eval_jacobian(torch.from_numpy(mp).to(pb.device))
+        if matrix_free:
+            _, err = pb.eval_gradient(torch.from_numpy(mp).to(pb.device), want_grad=False)
+        else:
+            _, _, err = pb.eval_jacobian(torch.from_numpy(mp).to(pb.device))
         e = err.cpu().numpy()
         return float(e[0]) if single else e
 
@@ -526,8 +531,16 @@ class SkeletonSolverFunction(SolverFunction):
         r = res.cpu().numpy()
         return (r[0], J[0]) if single else (r, J)
 
-    def get_gradient(self, model_parameters):
-        """2 J^T r (error_function_helpers.cpp:220)."""
+    def get_gradient(self, model_parameters, matrix_free: bool = False):
+        """2 J^T r (error_function_helpers.cpp:220).  matrix_free: formed on the GPU through the skeleton tree without a
+        Jacobian (mmx_eval_gradient; float32, MmxError for a problem outside its scope, never a fallback); the default
+        contracts the explicit Jacobian on the host, as before."""
+        if matrix_free:
+            single, mp = self._params(model_parameters)
+            pb, torch = self.lower(mp.shape[0])
+            grad, _ = pb.eval_gradient(torch.from_numpy(mp).to(pb.device), want_err=False)
+            g = grad.cpu().numpy()
+            return g[0] if single else g
         r, J = self.get_jacobian(model_parameters)
         return 2.0 * np.einsum("...mp,...m->...p", J, r)
 
