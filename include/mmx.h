@@ -846,6 +846,9 @@ int32_t mmx_solve_frames_host(
  *               per-instance rig, losses, per-element function weights):
  *                 grad_dev [B][P]  grad[b][p] = 2 sum_i J[b][i][p] r[b][i].  All P entries of every row are written; the
  *                                  entries of disabled parameters and of structurally zero columns are exact zeros.
+ *                                  (Also where J itself has an entry in a disabled column: a row of MMX_LIMIT_MINMAX_JOINT /
+ *                                  MMX_LIMIT_LINEAR_JOINT carries every column of its transform row, enabled or not, like
+ *                                  the reference's; a solve drops those columns, and so does the gradient.)
  *                 err_dev  [B]     the error mmx_eval_jacobian reports (under a robust loss the loss value, not |r|^2).
  *               The forward kinematics is the solve kernels' (pointer-jumping rounds in double), so err is the error a
  *               solve reports at theta; mmx_eval_jacobian keeps single-precision rounds, the two agree to rounding.

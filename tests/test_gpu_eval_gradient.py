@@ -118,10 +118,14 @@ def _case(name):
 @functools.lru_cache(maxsize=None)
 def _reference(name):
     """(g64 [B,P], e64 [B], g32 [B,P], e32 [B]) of a case from the oracle; computed once, never modified."""
+    return _reference_of(_case(name))
+
+
+def _reference_of(c):
+    """The same of a case dict (tests/test_gpu_eval_gradient_shapes.py builds its own cases)."""
     from oracle import oracle as orc
 
     orc.build()
-    c = _case(name)
     B, P = c["B"], c["rig"].num_params
     g64, g32, e64, e32 = np.zeros((B, P)), np.zeros((B, P), np.float32), np.zeros(B), np.zeros(B)
     for b in range(B):
