@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "mmx_constraint_intake.hpp"
 #include "mmx_host_tables.hpp"
 #include "mmx_kernels.hpp"
 #include "mmx_solve_plan.hpp"
@@ -149,6 +150,47 @@ hipError_t upload(DevBuf& buf, const std::vector<T>& v) {
   return hipMemcpy(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
+// Brings the arrays a setter is handed (float or int32 payload, all of one memory kind) to the device: null or empty -> null;
+// MMX_MEM_DEVICE -> the caller's pointer, borrowed; MMX_MEM_HOST -> copied into the handle's buffer ON THE CALLER'S STREAM, so
+// ordered after the kernels in flight there that still read the previous payload (torch's streams do not wait for the null
+// stream).  The host copies are complete -- the caller may free its arrays -- once finish() has returned; a setter that leaves
+// early with an error waits in the destructor.
+struct Staging {
+  int32_t memory;
+  hipStream_t stream;
+  bool pending = false;
+  Staging(int32_t memory_, hipStream_t stream_) : memory(memory_), stream(stream_) {}
+  Staging(const Staging&) = delete;
+  Staging& operator=(const Staging&) = delete;
+  ~Staging() {
+    (void)finish();
+  }
+  template <class T>
+  hipError_t bring(DevBuf& buf, const T* src, size_t count, const T*& dst) {
+    static_assert(sizeof(T) == 4, "float and int32 payloads");
+    dst = nullptr;
+    if (src == nullptr || count == 0) {
+      return hipSuccess;
+    }
+    if (memory == MMX_MEM_DEVICE) {
+      dst = src;
+      return hipSuccess;
+    }
+    hipError_t e = buf.ensure(count * sizeof(T));
+    if (e != hipSuccess) {
+      return e;
+    }
+    dst = buf.as<T>();
+    pending = true;
+    return hipMemcpyAsync(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice, stream);
+  }
+  hipError_t finish() {
+    const bool wait = pending;
+    pending = false;
+    return wait ? hipStreamSynchronize(stream) : hipSuccess;
+  }
+};
+
 } // namespace
 
 namespace mmx {
@@ -202,14 +244,12 @@ struct mmx_problem {
   // constraint payload: owned copies (host ingest) or borrowed device pointers
   DevBuf oPosOffset, oPosTarget, oPosWeight, oOriOffset, oOriTarget, oOriWeight, oMpTarget, oMpWeights, dLimits, dEnabledMask, oFnWeights;
   std::vector<mmx_parameter_limit> limits; // host copy (solve-list bookkeeping)
-  // further joint-constraint blocks: host copy of the descriptors (payload pointers cleared) and parents
-  struct JointBlockHost {
-    int32_t type = 0, count = 0;
-    std::vector<int32_t> parent;
-    std::vector<int32_t> parentB; // MMX_JC_JOINT_TO_JOINT_DISTANCE: the second joint of every constraint, else empty
-    DevBuf oLocalPoint, oLocalDir, oGlobal, oPlaneD, oWeight, oProjection; // owned copies of a host payload
+  // further joint-constraint blocks: their topology (host copy) and, per block, the owned copies of a host payload
+  std::vector<mmx::ProblemTopology::Block> blocks;
+  struct BlockPayload {
+    DevBuf oLocalPoint, oLocalDir, oGlobal, oPlaneD, oWeight, oProjection;
   };
-  std::vector<std::unique_ptr<JointBlockHost>> blocks;
+  std::vector<std::unique_ptr<BlockPayload>> blockPayload; // [blocks.size()]
   std::vector<mmx::JointBlockDev> blockDev;
   std::vector<mmx_ellipsoid_limit> ellipsoids; // host copy
   DevBuf dEllipsoids;
@@ -270,13 +310,23 @@ mmx::ProblemTopology problemTopology(const mmx_problem* pb) {
   p.instOri = pb->instOri;
   p.unionPos = pb->unionPos;
   p.unionOri = pb->unionOri;
-  for (const auto& h : pb->blocks) {
-    p.blocks.push_back(mmx::ProblemTopology::Block{h->type, h->parent, h->parentB});
-  }
+  p.blocks = pb->blocks;
   p.ellipsoids = pb->ellipsoids;
   p.limits = pb->limits;
   p.hasModel = pb->dev.hasModel != 0;
   return p;
+}
+
+// The host unit's loss record (mmx_constraint_intake.hpp) as the kernels take it
+mmx::LossDev lossDev(const mmx::LossHost& l) {
+  static_assert(
+      sizeof(mmx::LossHost) == sizeof(mmx::LossDev) && offsetof(mmx::LossHost, type) == offsetof(mmx::LossDev, type) &&
+          offsetof(mmx::LossHost, alpha) == offsetof(mmx::LossDev, alpha) && offsetof(mmx::LossHost, invC2) == offsetof(mmx::LossDev, invC2) &&
+          offsetof(mmx::LossHost, c) == offsetof(mmx::LossDev, c),
+      "loss layouts must match");
+  mmx::LossDev d;
+  std::memcpy(&d, &l, sizeof(d));
+  return d;
 }
 
 // mmx_ellipsoid_limit + the joint words of JointTables (full or renumbered) = the device record
@@ -992,16 +1042,11 @@ int32_t mmx_problem_create(
   if ((num_pos > 0 && pos_parent == nullptr) || (num_ori > 0 && ori_parent == nullptr)) {
     return fail(MMX_ERR_INVALID_ARGUMENT, "constraint parent array is null");
   }
-  for (int32_t c = 0; c < num_pos; ++c) {
-    // MT_CHECK(jntIndex < skeleton_.joints.size()) (joint_error_function-inl.h:230)
-    if (pos_parent[c] < 0 || pos_parent[c] >= rig->J) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, "position constraint parent joint out of range");
-    }
+  if (!mmx::jointsInRange(pos_parent, size_t(num_pos), rig->J)) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "position constraint parent joint out of range");
   }
-  for (int32_t c = 0; c < num_ori; ++c) {
-    if (ori_parent[c] < 0 || ori_parent[c] >= rig->J) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, "orientation constraint parent joint out of range");
-    }
+  if (!mmx::jointsInRange(ori_parent, size_t(num_ori), rig->J)) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "orientation constraint parent joint out of range");
   }
   mmx_problem* pb = new (std::nothrow) mmx_problem();
   if (pb == nullptr) {
@@ -1131,30 +1176,12 @@ int32_t mmx_problem_set_instance_rig(mmx_problem* pb, const float* translation_o
     return fail(MMX_ERR_INVALID_ARGUMENT, "instance rig: unknown memory space");
   }
   MMX_HIP(hipSetDevice(pb->rig->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t B = size_t(pb->B), J = size_t(pb->rig->J);
-  auto bring = [&](DevBuf& buf, const float* src, size_t count, const float*& dst) -> hipError_t {
-    if (src == nullptr) {
-      dst = nullptr;
-      return hipSuccess;
-    }
-    if (memory == MMX_MEM_DEVICE) {
-      dst = src;
-      return hipSuccess;
-    }
-    hipError_t e = buf.ensure(count * sizeof(float));
-    if (e != hipSuccess) {
-      return e;
-    }
-    dst = buf.as<float>();
-    return hipMemcpyAsync(buf.p, src, count * sizeof(float), hipMemcpyHostToDevice, s);
-  };
+  Staging stage(memory, static_cast<hipStream_t>(stream));
   const float *off = nullptr, *pre = nullptr;
-  MMX_HIP(bring(pb->oInstOffset, translation_offset, B * J * 3, off));
-  MMX_HIP(bring(pb->oInstPreRot, pre_rotation, B * J * 4, pre));
-  if (memory == MMX_MEM_HOST) {
-    MMX_HIP(hipStreamSynchronize(s)); // the caller may free its host arrays on return
-  }
+  MMX_HIP(stage.bring(pb->oInstOffset, translation_offset, B * J * 3, off));
+  MMX_HIP(stage.bring(pb->oInstPreRot, pre_rotation, B * J * 4, pre));
+  MMX_HIP(stage.finish());
   pb->rigDev.instOffset = off;
   pb->rigDev.instPreRot = pre;
   return MMX_OK;
@@ -1189,57 +1216,21 @@ int32_t mmx_problem_set_instance_parents(mmx_problem* pb, const int32_t* pos_par
   };
   MMX_HIP(fetch(pos_parent, B * size_t(pb->Kp), hp));
   MMX_HIP(fetch(ori_parent, B * size_t(pb->Ko), ho));
-  // validate everything before anything is modified (MT_CHECK joint_error_function-inl.h:230)
-  std::vector<uint8_t> seenP(size_t(pb->rig->J), 0), seenO(size_t(pb->rig->J), 0);
-  for (int32_t j : hp) {
-    if (j < 0 || j >= pb->rig->J) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, "instance parents: position constraint parent joint out of range");
-    }
-    seenP[size_t(j)] = 1;
+  // everything is validated before anything is modified
+  mmx::InstanceParentsIntake in = mmx::intakeInstanceParents(
+      pb->rig->J, hp, ho, memory == MMX_MEM_HOST,
+      {pb->instPos, pb->instOri, pb->unionPos, pb->unionOri, pb->instParentsFromHost, pb->instPosHost, pb->instOriHost, pb->tablesDirty});
+  if (in.code != MMX_OK) {
+    return fail(in.code, in.message);
   }
-  for (int32_t j : ho) {
-    if (j < 0 || j >= pb->rig->J) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, "instance parents: orientation constraint parent joint out of range");
-    }
-    seenO[size_t(j)] = 1;
-  }
-  // unchanged lists (the C++ shell re-sends them with every constraint update): nothing to do
-  if (memory == MMX_MEM_HOST && !pb->tablesDirty && pb->instParentsFromHost && hp == pb->instPosHost && ho == pb->instOriHost) {
+  if (in.unchanged) {
     return MMX_OK;
   }
-  auto place = [&](DevBuf& buf, const int32_t* src, const std::vector<int32_t>& host, const int32_t*& dst) -> hipError_t {
-    if (host.empty()) {
-      dst = nullptr;
-      return hipSuccess;
-    }
-    if (memory == MMX_MEM_DEVICE) {
-      dst = src;
-      return hipSuccess;
-    }
-    hipError_t e = buf.ensure(host.size() * sizeof(int32_t));
-    if (e != hipSuccess) {
-      return e;
-    }
-    dst = buf.as<int32_t>();
-    // on the caller's stream: ordered after the kernels in flight there that still read the previous lists
-    e = hipMemcpyAsync(buf.p, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    return e != hipSuccess ? e : hipStreamSynchronize(s);
-  };
+  Staging stage(memory, s);
   const int32_t *dp = nullptr, *dq = nullptr;
-  MMX_HIP(place(pb->oInstPosParent, pos_parent, hp, dp));
-  MMX_HIP(place(pb->oInstOriParent, ori_parent, ho, dq));
-  std::vector<int32_t> unionPos, unionOri;
-  for (int32_t j = 0; j < pb->rig->J; ++j) {
-    if (seenP[size_t(j)]) {
-      unionPos.push_back(j);
-    }
-    if (seenO[size_t(j)]) {
-      unionOri.push_back(j);
-    }
-  }
-  // the integer bookkeeping (solve list, structurally zero columns) depends on the UNION of the batch's parents only:
-  // new lists over the same joints need no rebuild -- the kernels read the lists themselves
-  const bool sameTables = !pb->tablesDirty && (dp != nullptr) == pb->instPos && (dq != nullptr) == pb->instOri && unionPos == pb->unionPos && unionOri == pb->unionOri;
+  MMX_HIP(stage.bring(pb->oInstPosParent, pos_parent, hp.size(), dp));
+  MMX_HIP(stage.bring(pb->oInstOriParent, ori_parent, ho.size(), dq));
+  MMX_HIP(stage.finish());
   pb->dev.instPosParent = dp;
   pb->dev.instOriParent = dq;
   pb->instPos = dp != nullptr;
@@ -1247,12 +1238,12 @@ int32_t mmx_problem_set_instance_parents(mmx_problem* pb, const int32_t* pos_par
   pb->instParentsFromHost = memory == MMX_MEM_HOST;
   pb->instPosHost = std::move(hp);
   pb->instOriHost = std::move(ho);
-  if (sameTables) {
+  if (in.sameTables) {
     return MMX_OK;
   }
   pb->tablesDirty = true;
-  pb->unionPos = std::move(unionPos);
-  pb->unionOri = std::move(unionOri);
+  pb->unionPos = std::move(in.unionPos);
+  pb->unionOri = std::move(in.unionOri);
   rc = uploadProblemTables(pb); // solve list, structurally zero columns: over the union of the batch
   if (rc != MMX_OK) {
     return rc;
@@ -1280,294 +1271,87 @@ int32_t mmx_problem_set_constraints_sized(mmx_problem* pb, const mmx_constraint_
 
 int32_t mmx_problem_set_constraints(mmx_problem* pb, const mmx_constraint_data* c, void* stream) {
   MMX_ZONE("mmx_problem_set_constraints");
-  int32_t rc = checkProblem(pb, false);
-  if (rc != MMX_OK) {
-    return rc;
-  }
-  if (c == nullptr) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "constraint data is null");
-  }
-  if (pb->Kp > 0 && (!c->pos_offset || !c->pos_target || !c->pos_weight)) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "position constraint arrays are null");
-  }
-  if (pb->Ko > 0 && (!c->ori_offset || !c->ori_target || !c->ori_weight)) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "orientation constraint arrays are null");
+  MMX_TRY(checkProblem(pb, false));
+  // ---- every check, every derived integer and the comparison with the last accepted call (mmx_constraint_intake.cpp):
+  // everything is validated before anything is modified
+  const mmx_rig_desc rigDesc = pb->rig->desc();
+  mmx::ConstraintIntake in =
+      mmx::intakeConstraints(rigDesc, pb->Kp, pb->Ko, c, {pb->blocks, pb->ellipsoids, pb->limits, pb->dev.hasModel != 0, pb->tablesDirty});
+  if (in.code != MMX_OK) {
+    return fail(in.code, in.message);
   }
   MMX_HIP(hipSetDevice(pb->rig->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
   mmx::ProblemDev& d = pb->dev;
-  const size_t B = size_t(pb->B);
-  if (c->memory != MMX_MEM_DEVICE && c->memory != MMX_MEM_HOST) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "constraint data: unknown memory space");
-  }
-  auto makeLoss = [](float alpha, float cc) { // GeneralizedLossT ctor (generalized_loss.cpp:81-101), kEps = 1e-9
-    mmx::LossDev l{0, 2.f, 1.f, 1.f};
-    if (cc > 0.f) {
-      l.alpha = alpha;
-      l.invC2 = 1.f / (cc * cc);
-      l.c = cc;
-      const float kEps = 1e-9f;
-      if (alpha >= 2.f - kEps && alpha <= 2.f + kEps) {
-        l.type = 0;
-      } else if (alpha >= 1.f - kEps && alpha <= 1.f + kEps) {
-        l.type = 1;
-      } else if (alpha >= -kEps && alpha <= kEps) {
-        l.type = 2;
-      } else if (alpha == MMX_LOSS_WELSCH) {
-        l.type = 3;
-      } else {
-        l.type = 4;
-      }
-    }
-    return l;
-  };
-  // ---- optional parameter-space blocks
-  const int32_t P = pb->rig->P;
-  if (c->num_limits < 0 || (c->num_limits > 0 && c->limits == nullptr)) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "limits: negative count or null array");
-  }
-  if ((c->model_target == nullptr) != (c->model_weights == nullptr)) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "model_target and model_weights must be given together");
-  }
-  const mmx_rig_desc rigDesc = pb->rig->desc();
-  for (int32_t l = 0; l < c->num_limits; ++l) {
-    const mmx_parameter_limit& lm = c->limits[l];
-    const bool model = lm.type == MMX_LIMIT_MINMAX || lm.type == MMX_LIMIT_LINEAR || lm.type == MMX_LIMIT_HALFPLANE;
-    const bool joint = lm.type == MMX_LIMIT_MINMAX_JOINT || lm.type == MMX_LIMIT_LINEAR_JOINT;
-    const bool two = lm.type == MMX_LIMIT_LINEAR || lm.type == MMX_LIMIT_HALFPLANE || lm.type == MMX_LIMIT_LINEAR_JOINT;
-    if (lm.type == MMX_LIMIT_MINMAX_JOINT_PASSIVE) {
-      continue; // LimitErrorFunctionT skips the passive type: no error, no row (limit_error_function.cpp:836-837,1051-1052)
-    }
-    if (!model && !joint) {
-      return fail(
-          MMX_ERR_UNSUPPORTED,
-          "limit " + std::to_string(l) +
-              ": MinMax, MinMaxJoint, MinMaxJointPassive (ignored like in the reference), Linear, LinearJoint and HalfPlane go here; "
-              "Ellipsoid limits travel in mmx_constraint_data::ellipsoid_limits");
-    }
-    const int32_t bound = joint ? MMX_PARAMS_PER_JOINT * pb->rig->J : P;
-    if (lm.index0 < 0 || lm.index0 >= bound || (two && (lm.index1 < 0 || lm.index1 >= bound))) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, "limit " + std::to_string(l) + ": parameter index out of range"); // MT_CHECK :574-575,:611-612
-    }
-    if (mmx::limitParameters(&rigDesc, lm).size() > 4) {
-      return fail(MMX_ERR_UNSUPPORTED, "limit " + std::to_string(l) + ": more than four model parameters drive the limited joint parameters");
-    }
-  }
-  if (c->num_function_weights < 0 || c->num_function_weights > 4 + MMX_MAX_JOINT_BLOCKS) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "num_function_weights out of range (columns: position, orientation, limits, model parameters, joint blocks)");
-  }
-  // ---- further joint-constraint blocks
-  if (c->num_joint_blocks < 0 || c->num_joint_blocks > MMX_MAX_JOINT_BLOCKS || (c->num_joint_blocks > 0 && c->joint_blocks == nullptr)) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "joint_blocks: count out of range or null array");
-  }
-  bool blocksChanged = size_t(c->num_joint_blocks) != pb->blocks.size();
-  int32_t genRows = 0, genCount = 0;
-  for (int32_t i = 0; i < c->num_joint_blocks; ++i) {
-    const mmx_joint_constraint_block& jb = c->joint_blocks[i];
-    const std::string tag = "joint block " + std::to_string(i);
-    if (jb.type < MMX_JC_PLANE || jb.type > MMX_JC_JOINT_TO_JOINT_DISTANCE) {
-      return fail(MMX_ERR_UNSUPPORTED, tag + ": unknown error-function type");
-    }
-    const bool pointOnly = jb.type == MMX_JC_PROJECTION || jb.type == MMX_JC_DISTANCE; // (ABI 12)
-    const bool pairType = jb.type == MMX_JC_JOINT_TO_JOINT_DISTANCE; // two points: parent is [2 * count], local_dir the second offset
-    if ((pointOnly || pairType) && jb.loss_c > 0.f && !(jb.loss_alpha == 2.f && jb.loss_c == 1.f)) {
-      return fail(MMX_ERR_UNSUPPORTED, tag + ": projection / distance / joint-to-joint distance blocks take the L2 loss only (loss_c <= 0 or (alpha, c) = (2, 1))");
-    }
-    if (jb.type == MMX_JC_PROJECTION && !std::isfinite(jb.near_clip)) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": near_clip is not finite");
-    }
-    if (jb.count < 0 || (jb.count > 0 && (jb.parent == nullptr || (!pairType && jb.global == nullptr) || jb.weight == nullptr))) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": negative count or null parent / global / weight array");
-    }
-    const bool plane = jb.type == MMX_JC_PLANE || jb.type == MMX_JC_HALF_PLANE;
-    const bool fixedAxis = jb.type == MMX_JC_FIXED_AXIS_DIFF || jb.type == MMX_JC_FIXED_AXIS_COS || jb.type == MMX_JC_FIXED_AXIS_ANGLE;
-    const bool needD = plane || jb.type == MMX_JC_DISTANCE || pairType;
-    if (jb.count > 0 && ((!fixedAxis && jb.local_point == nullptr) || (!plane && !pointOnly && jb.local_dir == nullptr) || (needD && jb.plane_d == nullptr))) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": a payload array its error function needs is null");
-    }
-    if (jb.count > 0 && jb.type == MMX_JC_PROJECTION && jb.projection == nullptr) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": projection block without its projection matrices");
-    }
-    const int32_t numParents = pairType ? 2 * jb.count : jb.count;
-    for (int32_t k = 0; k < numParents; ++k) {
-      if (jb.parent[k] < 0 || jb.parent[k] >= pb->rig->J) {
-        return fail(MMX_ERR_INVALID_ARGUMENT, tag + ": parent joint out of range"); // MT_CHECK joint_error_function-inl.h:230
-      }
-    }
-    genRows += mmx::jointBlockFuncDim(jb.type) * jb.count;
-    genCount += jb.count;
-    if (!blocksChanged) {
-      const mmx_problem::JointBlockHost& h = *pb->blocks[size_t(i)];
-      blocksChanged = h.type != jb.type || h.count != jb.count || !std::equal(h.parent.begin(), h.parent.end(), jb.parent) ||
-          h.parentB.size() != size_t(numParents - jb.count) || !std::equal(h.parentB.begin(), h.parentB.end(), jb.parent + jb.count);
-    }
-  }
-  if (genCount > 1024) {
-    return fail(MMX_ERR_UNSUPPORTED, "more than 1024 constraints in the further joint-constraint blocks");
-  }
-  // ---- Ellipsoid entries of the limit block
-  if (c->num_ellipsoid_limits < 0 || c->num_ellipsoid_limits > 256 || (c->num_ellipsoid_limits > 0 && c->ellipsoid_limits == nullptr)) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "ellipsoid_limits: count out of range or null array");
-  }
-  for (int32_t i = 0; i < c->num_ellipsoid_limits; ++i) {
-    const mmx_ellipsoid_limit& e = c->ellipsoid_limits[i];
-    if (e.parent < 0 || e.parent >= pb->rig->J || e.ellipsoid_parent < 0 || e.ellipsoid_parent >= pb->rig->J) {
-      return fail(MMX_ERR_INVALID_ARGUMENT, "ellipsoid limit " + std::to_string(i) + ": joint index out of range");
-    }
-  }
-  // ---- everything above only validated; from here on the problem is modified.  Should a device
-  // call fail half-way, tablesDirty keeps the derived tables from being trusted by the next call.
-  if (c->memory == MMX_MEM_DEVICE) {
-    d.posOffset = c->pos_offset;
-    d.posTarget = c->pos_target;
-    d.posWeight = c->pos_weight;
-    d.oriOffset = c->ori_offset;
-    d.oriTarget = c->ori_target;
-    d.oriWeight = c->ori_weight;
-  } else if (c->memory == MMX_MEM_HOST) {
-    auto ingest = [&](DevBuf& buf, const float* src, size_t count, const float*& dst) -> hipError_t {
-      if (count == 0) {
-        dst = nullptr;
-        return hipSuccess;
-      }
-      hipError_t e = buf.ensure(count * sizeof(float));
-      if (e != hipSuccess) {
-        return e;
-      }
-      dst = buf.as<float>();
-      return hipMemcpyAsync(buf.p, src, count * sizeof(float), hipMemcpyHostToDevice, s);
-    };
-    MMX_HIP(ingest(pb->oPosOffset, c->pos_offset, B * pb->Kp * 3, d.posOffset));
-    MMX_HIP(ingest(pb->oPosTarget, c->pos_target, B * pb->Kp * 3, d.posTarget));
-    MMX_HIP(ingest(pb->oPosWeight, c->pos_weight, B * pb->Kp, d.posWeight));
-    MMX_HIP(ingest(pb->oOriOffset, c->ori_offset, B * pb->Ko * 4, d.oriOffset));
-    MMX_HIP(ingest(pb->oOriTarget, c->ori_target, B * pb->Ko * 4, d.oriTarget));
-    MMX_HIP(ingest(pb->oOriWeight, c->ori_weight, B * pb->Ko, d.oriWeight));
-    if (c->function_weights != nullptr && c->num_function_weights > 0) {
-      MMX_HIP(ingest(pb->oFnWeights, c->function_weights, B * size_t(c->num_function_weights), d.fnWeights));
-    }
-    MMX_HIP(hipStreamSynchronize(s)); // the caller may free its host arrays on return
-  }
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P);
+  // ---- the payload.  From here on the problem is modified; should a device call fail half-way, tablesDirty -- set before the
+  // handle's topology first differs from the derived tables -- keeps them from being trusted by the next call.
+  Staging stage(c->memory, static_cast<hipStream_t>(stream));
+  MMX_HIP(stage.bring(pb->oPosOffset, c->pos_offset, B * pb->Kp * 3, d.posOffset));
+  MMX_HIP(stage.bring(pb->oPosTarget, c->pos_target, B * pb->Kp * 3, d.posTarget));
+  MMX_HIP(stage.bring(pb->oPosWeight, c->pos_weight, B * pb->Kp, d.posWeight));
+  MMX_HIP(stage.bring(pb->oOriOffset, c->ori_offset, B * pb->Ko * 4, d.oriOffset));
+  MMX_HIP(stage.bring(pb->oOriTarget, c->ori_target, B * pb->Ko * 4, d.oriTarget));
+  MMX_HIP(stage.bring(pb->oOriWeight, c->ori_weight, B * pb->Ko, d.oriWeight));
   // per-element error-function weights (errorFunctionWeights[iBatch][...] of the batched driver)
-  if (c->function_weights != nullptr && c->num_function_weights > 0) {
-    if (c->memory == MMX_MEM_DEVICE) {
-      d.fnWeights = c->function_weights;
-    }
-    d.fnCols = c->num_function_weights;
-  } else {
-    d.fnWeights = nullptr;
-    d.fnCols = 0;
-  }
-  d.wPos = c->pos_function_weight;
-  d.wOri = c->ori_function_weight;
-  d.lossPos = makeLoss(c->pos_loss_alpha, c->pos_loss_c);
-  d.lossOri = makeLoss(c->ori_loss_alpha, c->ori_loss_c);
-  if (blocksChanged) {
+  MMX_HIP(stage.bring(pb->oFnWeights, c->function_weights, B * size_t(in.fnCols), d.fnWeights));
+  MMX_HIP(stage.bring(pb->oMpTarget, c->model_target, B * P, d.mpTarget));
+  MMX_HIP(stage.bring(pb->oMpWeights, c->model_weights, B * P, d.mpWeights));
+  if (in.blocksChanged) {
     pb->tablesDirty = true;
-    pb->blocks.clear();
-    for (int32_t i = 0; i < c->num_joint_blocks; ++i) {
-      auto h = std::make_unique<mmx_problem::JointBlockHost>();
-      h->type = c->joint_blocks[i].type;
-      h->count = c->joint_blocks[i].count;
-      h->parent.assign(c->joint_blocks[i].parent, c->joint_blocks[i].parent + h->count);
-      if (h->type == MMX_JC_JOINT_TO_JOINT_DISTANCE) {
-        h->parentB.assign(c->joint_blocks[i].parent + h->count, c->joint_blocks[i].parent + 2 * h->count);
-      }
-      pb->blocks.push_back(std::move(h));
+    pb->blocks = std::move(in.blocks);
+    pb->blockPayload.clear();
+    for (size_t i = 0; i < pb->blocks.size(); ++i) {
+      pb->blockPayload.push_back(std::make_unique<mmx_problem::BlockPayload>());
     }
   }
-  pb->blockDev.assign(size_t(c->num_joint_blocks), mmx::JointBlockDev{});
-  {
-    int32_t first = 0, row = 3 * pb->U;
-    for (int32_t i = 0; i < c->num_joint_blocks; ++i) {
-      const mmx_joint_constraint_block& jb = c->joint_blocks[i];
-      mmx_problem::JointBlockHost& h = *pb->blocks[size_t(i)];
-      mmx::JointBlockDev& k = pb->blockDev[size_t(i)];
-      k.type = jb.type;
-      k.count = jb.count;
-      k.first = first;
-      k.rowStart = row;
-      k.fw = jb.function_weight;
-      k.loss = makeLoss(jb.loss_alpha, jb.loss_c);
-      k.nearClip = jb.type == MMX_JC_PROJECTION ? jb.near_clip : 0.f;
-      const size_t cnt = B * size_t(jb.count);
-      auto bring = [&](DevBuf& buf, const float* src, size_t count, const float*& dst) -> hipError_t {
-        if (src == nullptr || count == 0) {
-          dst = nullptr;
-          return hipSuccess;
-        }
-        if (c->memory == MMX_MEM_DEVICE) {
-          dst = src;
-          return hipSuccess;
-        }
-        hipError_t e = buf.ensure(count * sizeof(float));
-        if (e != hipSuccess) {
-          return e;
-        }
-        dst = buf.as<float>();
-        return hipMemcpy(buf.p, src, count * sizeof(float), hipMemcpyHostToDevice);
-      };
-      MMX_HIP(bring(h.oLocalPoint, jb.local_point, 3 * cnt, k.localPoint));
-      MMX_HIP(bring(h.oLocalDir, jb.local_dir, 3 * cnt, k.localDir));
-      MMX_HIP(bring(h.oGlobal, jb.global, 3 * cnt, k.global));
-      MMX_HIP(bring(h.oPlaneD, jb.plane_d, cnt, k.planeD));
-      MMX_HIP(bring(h.oWeight, jb.weight, cnt, k.weight));
-      MMX_HIP(bring(h.oProjection, jb.type == MMX_JC_PROJECTION ? jb.projection : nullptr, 12 * cnt, k.projection));
-      first += jb.count;
-      row += mmx::jointBlockFuncDim(jb.type) * jb.count;
-    }
+  pb->blockDev.assign(pb->blocks.size(), mmx::JointBlockDev{});
+  for (size_t i = 0; i < pb->blocks.size(); ++i) {
+    const mmx_joint_constraint_block& jb = c->joint_blocks[i];
+    mmx_problem::BlockPayload& h = *pb->blockPayload[i];
+    mmx::JointBlockDev& k = pb->blockDev[i];
+    k.type = jb.type;
+    k.count = jb.count;
+    k.first = in.blockRows[i].first;
+    k.rowStart = in.blockRows[i].rowStart;
+    k.fw = jb.function_weight;
+    k.loss = lossDev(in.blockRows[i].loss);
+    k.nearClip = in.blockRows[i].nearClip;
+    const size_t cnt = B * size_t(jb.count);
+    MMX_HIP(stage.bring(h.oLocalPoint, jb.local_point, 3 * cnt, k.localPoint));
+    MMX_HIP(stage.bring(h.oLocalDir, jb.local_dir, 3 * cnt, k.localDir));
+    MMX_HIP(stage.bring(h.oGlobal, jb.global, 3 * cnt, k.global));
+    MMX_HIP(stage.bring(h.oPlaneD, jb.plane_d, cnt, k.planeD));
+    MMX_HIP(stage.bring(h.oWeight, jb.weight, cnt, k.weight));
+    MMX_HIP(stage.bring(h.oProjection, jb.type == MMX_JC_PROJECTION ? jb.projection : nullptr, 12 * cnt, k.projection));
   }
-  pb->genRows = genRows;
-  const bool ellipsoidsChanged = size_t(c->num_ellipsoid_limits) != pb->ellipsoids.size() ||
-      (c->num_ellipsoid_limits > 0 &&
-       std::memcmp(c->ellipsoid_limits, pb->ellipsoids.data(), size_t(c->num_ellipsoid_limits) * sizeof(mmx_ellipsoid_limit)) != 0);
+  MMX_HIP(stage.finish()); // the caller may free its host arrays on return
+  // ---- the descriptors, from the record
+  pb->tablesDirty = pb->tablesDirty || in.structureChanged;
   pb->ellipsoids.assign(c->ellipsoid_limits, c->ellipsoid_limits + c->num_ellipsoid_limits);
-  std::vector<mmx_parameter_limit> kept; // the limits that produce a row (the passive type does not)
-  for (int32_t l = 0; l < c->num_limits; ++l) {
-    if (c->limits[l].type != MMX_LIMIT_MINMAX_JOINT_PASSIVE) {
-      kept.push_back(c->limits[l]);
-    }
-  }
-  const bool structureChanged = pb->tablesDirty || blocksChanged || ellipsoidsChanged || (c->model_target != nullptr) != (d.hasModel != 0) || kept.size() != pb->limits.size() ||
-      (!kept.empty() && std::memcmp(kept.data(), pb->limits.data(), kept.size() * sizeof(mmx_parameter_limit)) != 0);
-  pb->tablesDirty = pb->tablesDirty || structureChanged;
-  pb->limits = std::move(kept);
+  pb->limits = std::move(in.limits);
+  pb->genRows = in.genRows;
+  pb->M = in.M;
   static_assert(sizeof(mmx_parameter_limit) == sizeof(mmx::LimitDev) && sizeof(mmx::LimitDev) == 32, "limit layouts must match");
   MMX_HIP(upload(pb->dLimits, pb->limits));
   d.NL = int32_t(pb->limits.size());
   d.limits = pb->dLimits.as<mmx::LimitDev>();
+  d.fnCols = in.fnCols;
+  d.wPos = c->pos_function_weight;
+  d.wOri = c->ori_function_weight;
   d.wLimit = c->limit_function_weight;
-  d.hasModel = c->model_target != nullptr ? 1 : 0;
   d.wModel = c->model_function_weight;
-  if (d.hasModel) {
-    if (c->memory == MMX_MEM_DEVICE) {
-      d.mpTarget = c->model_target;
-      d.mpWeights = c->model_weights;
-    } else {
-      MMX_HIP(pb->oMpTarget.ensure(B * P * sizeof(float)));
-      MMX_HIP(pb->oMpWeights.ensure(B * P * sizeof(float)));
-      MMX_HIP(hipMemcpy(pb->oMpTarget.p, c->model_target, B * P * sizeof(float), hipMemcpyHostToDevice));
-      MMX_HIP(hipMemcpy(pb->oMpWeights.p, c->model_weights, B * P * sizeof(float), hipMemcpyHostToDevice));
-      d.mpTarget = pb->oMpTarget.as<float>();
-      d.mpWeights = pb->oMpWeights.as<float>();
-    }
-  } else {
-    d.mpTarget = d.mpWeights = nullptr;
-  }
-  const int32_t rowsE = 3 * int32_t(pb->ellipsoids.size());
-  pb->M = 3 * pb->U + pb->genRows + rowsE + d.NL + (d.hasModel ? P : 0);
-  d.M = pb->M;
-  d.rowsJoint = 3 * pb->U + pb->genRows + rowsE;
-  if (!structureChanged) { // payload pointers / weights / losses of the blocks may still have changed
+  d.lossPos = lossDev(in.lossPos);
+  d.lossOri = lossDev(in.lossOri);
+  d.hasModel = in.hasModel ? 1 : 0;
+  d.M = in.M;
+  d.rowsJoint = in.rowsJoint;
+  // ---- the tables
+  if (in.structureChanged) { // the fused kernel's solve list and limit tables depend on it
+    MMX_TRY(uploadProblemTables(pb));
+    pb->tablesDirty = false;
+  } else { // payload pointers / weights / losses of the blocks may still have changed
     MMX_HIP(upload(pb->dBlocks, pb->blockDev));
     d.blocks = pb->dBlocks.as<mmx::JointBlockDev>();
-  }
-  if (structureChanged) { // the fused kernel's solve list and limit tables depend on it
-    rc = uploadProblemTables(pb);
-    if (rc != MMX_OK) {
-      return rc;
-    }
-    pb->tablesDirty = false;
   }
   pb->haveConstraints = true;
   return MMX_OK;

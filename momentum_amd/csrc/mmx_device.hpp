@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #include "../../include/mmx.h"
+#include "mmx_constraint_intake.hpp"
 
 namespace mmx {
 
@@ -776,7 +777,7 @@ __device__ __forceinline__ F3 normalizedOrSame(const F3& a) { // Eigen normalize
 
 // (host twin: jointBlockRows in mmx_capi.hip)
 __host__ __device__ __forceinline__ int jointBlockFuncDim(int type) {
-  return (type == MMX_JC_AIM_DIST || type == MMX_JC_AIM_DIR || type == MMX_JC_FIXED_AXIS_DIFF) ? 3 : type == MMX_JC_PROJECTION ? 2 : 1;
+  return jointBlockRows(type); // the one definition: mmx_constraint_intake.hpp
 }
 
 __device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k, const float* js, int joint, int joint2, size_t c) {
