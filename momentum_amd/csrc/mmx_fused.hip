@@ -347,7 +347,7 @@ struct FusedLayout {
   size_t auxOff; // where the latter three start inside it: 0, or behind uy when uy must survive the factorisation (separateUy)
   size_t cellOff; // where the partial cells start (counted from auxOff)
   size_t t9; // aligned kTan J: tanOwn at 0, jd and tanPre at t9, dfull at 2 t9 of the arena
-  size_t arenaFloats; // srcT (E-G, 14 channels) | the refinement's buffers + dfull (J-K)
+  size_t arenaFloats; // srcT (E-G, kSlotStride floats per slot) | the refinement's buffers + dfull (J-K)
   size_t umomFloats; // the unit moments' place, also the first-order subtree sums' (D-E)
   size_t regionFloats; // assembly scratch (A-G) | the factor's tiles
   size_t genFloats; // kGen: records, residual rows, w, J_g
@@ -370,9 +370,9 @@ __host__ __device__ inline FusedLayout fusedLayout(int NB, int J, int P, int U, 
   l.auxOff = separateUy ? a4(3 * size_t(U)) : 0;
   l.uyFloats = separateUy ? l.auxOff + aux : mx(a4(3 * size_t(U)), aux);
   l.t9 = a4(size_t(kTan) * J);
-  l.arenaFloats = mx(size_t(kSrcCh - 1) * size_t(srcStrideFor(nsrc)), 2 * l.t9 + a4(P));
+  l.arenaFloats = mx(slotTableFloats(nsrc), 2 * l.t9 + a4(P));
   if (mix) {
-    l.arenaFloats = mx(size_t(kSrcCh - 1) * size_t(srcStrideFor(nsrc)), a4(2 * (mixXDoubles(J, nsrc) + mixYDoubles(J, P))));
+    l.arenaFloats = mx(slotTableFloats(nsrc), a4(2 * (mixXDoubles(J, nsrc) + mixYDoubles(J, P))));
   }
   l.umomFloats = mx(a4(size_t(kUmom) * U), a4(size_t(kC1) * J));
   const size_t scratch = fkBufFloats(J) + 2 * a4(size_t(kC2) * J) + l.umomFloats;
@@ -1153,6 +1153,9 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       return r;
     };
     auto takeS = [&](size_t count) { return reinterpret_cast<int16_t*>(take((count + 1) / 2)); };
+    // (the layout's maxima are 64-bit compares, which only the vector unit has: without this the carve's pointers behind them,
+    // and every uniform offset added to one, live in vector registers for the whole launch)
+    auto uniform = [](size_t count) { return size_t(uint32_t(__builtin_amdgcn_readfirstlane(int(count)))); };
     s.mStart = takeS(NP + 1);
     s.mTin = reinterpret_cast<int*>(take(nsrc));
     s.mInfo = reinterpret_cast<int*>(take(nsrc));
@@ -1185,7 +1188,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       s.g = take(NP);
       s.d0 = take(NP);
     }
-    s.uy = take(lay.uyFloats);
+    s.uy = take(uniform(lay.uyFloats));
     s.rho = s.uy + lay.auxOff, s.invDiag = s.rho + NP, srcGu = s.rho, cells = s.rho + lay.cellOff;
     s.red = reinterpret_cast<double*>(take(kMix ? 40 : 16)); // (kMix: five sums per reduction round)
     s.flags = reinterpret_cast<int*>(take(8)); // [4 .. 6] as floats: the precision estimate's accumulators (estAcc below)
@@ -1197,7 +1200,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       s.gW = take(rowsGp);
       s.gJ = take(size_t(rowsGp) * size_t(srcStrideFor(NP)));
     }
-    arena = take(lay.arenaFloats); // srcT (phases E-G)  |  the refinement's buffers and dfull (phases J-K)
+    arena = take(uniform(lay.arenaFloats)); // srcT (phases E-G)  |  the refinement's buffers and dfull (phases J-K)
     if (kMix) { // ... | the double scratch X, Y (everywhere else)
       m.X = reinterpret_cast<double*>(arena);
       m.Y = m.X + mixXDoubles(JL, nsrc);
@@ -1209,7 +1212,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     s.fkB = reinterpret_cast<double*>(p); // over own2 / sub2 (2 kC2 J >= fkBufFloats(J) floats)
     s.own2 = take(size_t(kC2) * JL);
     s.sub2 = take(size_t(kC2) * JL);
-    s.umom = take(lay.umomFloats);
+    s.umom = take(uniform(lay.umomFloats));
     s.own1 = region, s.sub1 = s.umom; // phases D-E: over the FK buffer (dead after FK) / the unit moments (dead after the own sums)
     s.L = region;
     if (kMix) { // the double arrays, behind everything else (every offset so far is a multiple of 16 bytes)
@@ -1521,10 +1524,10 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     treeSum<kC2Used, true, kC2, kUnD>(fv, s.own2, s.sub2, J, wave, lane);
     __syncthreads();
     MMX_CLK(3)
-    // ================= E: per-slot tables (weight folded in), channel-major
-    const int sst = srcStrideFor(nsrc);
-    float* srcD = s.srcT; // [7][sst]  G0(3) AX(3) TR
-    float* srcA = s.srcT + 7 * sst; // [7][sst]  AL(3) BV(3) BS
+    // ================= E: per-slot tables (weight folded in), slot-major: kSlotStride floats per slot, so that a reader
+    // needs ONE address per slot and every channel is an immediate offset from it
+    float* srcD = s.srcT; // [nsrc][kSlotStride] + 0..6   G0(3) AX(3) TR
+    float* srcA = s.srcT + 7; // [nsrc][kSlotStride] + 7..13  AL(3) BV(3) BS
     float* srcG = srcGu; // [nsrc]    the slot's share of g = J^T r (in uy's place: dead since phase D, rho / invDiag not yet written)
     for (int e = tid; e < nsrc; e += 256) {
       ColumnSourceDev cs;
@@ -1582,14 +1585,17 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
         tr = dot(al, m1) + kLn2 * (sb[4] + sb[7] + sb[9]);
       }
       const float w = s.mW[e]; // pad slots: 0
-      float* d = srcD + e;
-      d[0] = w * g0.x, d[sst] = w * g0.y, d[2 * sst] = w * g0.z;
-      d[3 * sst] = w * ax.x, d[4 * sst] = w * ax.y, d[5 * sst] = w * ax.z;
-      d[6 * sst] = w * tr;
-      float* o = srcA + e;
-      o[0] = w * al.x, o[sst] = w * al.y, o[2 * sst] = w * al.z;
-      o[3 * sst] = w * bv.x, o[4 * sst] = w * bv.y, o[5 * sst] = w * bv.z;
-      o[6 * sst] = w * bs;
+      // (the fourteen values pass through opaque copies: their stores are adjacent now, and a vectoriser that starts from
+      // adjacent stores would pair and contract the arithmetic above differently than it did for the strided stores -- the
+      // slot values, and with them every result, stay bit for bit what they were)
+      float tv[kSlotStride] = {w * g0.x, w * g0.y, w * g0.z, w * ax.x, w * ax.y, w * ax.z, w * tr,
+                               w * al.x, w * al.y, w * al.z, w * bv.x, w * bv.y, w * bv.z, w * bs};
+      float* d = srcD + kSlotStride * e;
+#pragma unroll
+      for (int q = 0; q < kSlotStride; ++q) {
+        asm volatile("" : "+v"(tv[q]));
+        d[q] = tv[q];
+      }
       if (!kMix) {
         srcG[e] = w * sourceGradient(cs.joint, cs.dof, cs.parent, s.js, s.sub1 + kC1 * cs.tin);
       }
@@ -1629,7 +1635,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     //   w_r w_c (G0.AL + AX.BV + TR BS)(deep, ancestor),   deep = the slot whose joint lies below the other's,
     // i.e. one of the two 7-term products D_r . A_c or A_r . D_c, selected by the DFS intervals -- so every
     // 16 x 16 tile is two matrix-core products (K = 7 padded to 8: two v_mfma_f32_16x16x4_f32 each) of the
-    // channel-major slot tables, masked, and stored straight into the LDS tile (O(1) work per entry,
+    // slot tables, masked, and stored straight into the LDS tile (O(1) work per entry,
     // independent of the number of constraint rows; the scratch region became free at the barrier after
     // E).  The pairs that involve an extra source of a multi-source column are added afterwards from
     // host-built term records.
@@ -1644,10 +1650,13 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       auto loadOps = [&](int I, int Jc) {
         TileOps o;
         const int ri = 16 * I + i, ci = 16 * Jc + i;
-        o.dI0 = srcD[gq * sst + ri], o.aI0 = srcA[gq * sst + ri];
-        o.dJ0 = srcD[gq * sst + ci], o.aJ0 = srcA[gq * sst + ci];
-        o.dI1 = srcD[k1 * sst + ri], o.aI1 = srcA[k1 * sst + ri];
-        o.dJ1 = srcD[k1 * sst + ci], o.aJ1 = srcA[k1 * sst + ci];
+        // (stride 14: the 16 slots x 2 channels of a 32-lane group fall into 32 different banks)
+        const float* pr = srcD + kSlotStride * ri;
+        const float* pc = srcD + kSlotStride * ci;
+        o.dI0 = pr[gq], o.aI0 = pr[7 + gq];
+        o.dJ0 = pc[gq], o.aJ0 = pc[7 + gq];
+        o.dI1 = pr[k1], o.aI1 = pr[7 + k1];
+        o.dJ1 = pc[k1], o.aJ1 = pc[7 + k1];
         o.spanC = s.mTin[ci];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -1718,11 +1727,13 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
           const uint32_t x = rec[k].x;
           if (x & (1u << 26)) {
             const int deep = x & 0xfff, anc = (x >> 12) & 0xfff;
-            float dv[7], av[7]; // all fourteen reads in flight together: one LDS round trip per record
+            float dv[7], av[7]; // all fourteen reads in flight together: one LDS round trip per record, two addresses
+            const float* pd = srcD + kSlotStride * deep;
+            const float* pa = srcA + kSlotStride * anc;
 #pragma unroll
             for (int ch = 0; ch < 7; ++ch) {
-              dv[ch] = srcD[ch * sst + deep];
-              av[ch] = srcA[ch * sst + anc];
+              dv[ch] = pd[ch];
+              av[ch] = pa[ch];
             }
             float hj = 0.f;
 #pragma unroll
@@ -1956,6 +1967,11 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
           // the sixteen elimination steps; kGuard: a pivot at rounding level drops its column from this iteration's step
           // (see kPivotFloor): 1 / l_jj = 0
           auto chain = [&](const bool kGuard, const float floorRow) {
+            // (an opaque copy of the lane per run of the chain: the sixteen `lane == j` masks are then formed at their use --
+            // v_cmp + v_cndmask -- where the loop-invariant ones were parked in VGPR lanes after every panel's barrier and
+            // read back on the dependent chain)
+            int laneC = lane;
+            asm volatile("" : "+v"(laneC));
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
               const float djj = readLaneF(a[j], j);
@@ -1969,7 +1985,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
                 inv = djj > fl ? inv : (kMix ? __builtin_amdgcn_rsqf(fl) : 0.f);
               }
               a[j] *= inv;
-              if (lane == j) {
+              if (laneC == j) {
                 invd = inv;
               }
               panelRowUpdate(a, j);
@@ -2001,10 +2017,12 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
           // whole row and every row leaves as four unpredicated 16-byte stores.
           const bool stores = panelLane || (diagLane && wave == 0);
           float v[16];
+          int laneS = lane; // (opaque per panel, as in the chain: no parked `c > lane` masks)
+          asm volatile("" : "+v"(laneS));
 #pragma unroll
           for (int c = 0; c < 16; ++c) {
             const float partner = __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(a[c]), 0x401F));
-            v[c] = (diagLane && c > lane) ? partner : a[c];
+            v[c] = c > laneS ? partner : a[c]; // (c <= 15: only a diagonal lane has c > lane)
           }
           if (stores) {
 #pragma unroll

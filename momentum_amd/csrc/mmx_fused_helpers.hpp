@@ -49,7 +49,8 @@ struct FusedLds {
   float* sub2; // [kC2 J]
   float* L; // [T][256] tiles; a diagonal tile holds L_kk (lower triangle) and L_kk^-T (strict upper triangle)
   // ---- aliases the refinement scratch (dfull, jd, tanOwn, tanPre): dead before phase J starts
-  float* srcT; // [15][srcStride]: weighted D (7 channels) | weighted A (7) | weighted J^T r share (1), channel-major
+  float* srcT; // one-launch solve: [nsrc][kSlotStride] slot-major, per slot weighted D (7 channels) | weighted A (7); the tree
+  // kernels: [15][srcStride] channel-major, weighted D (7) | weighted A (7) | weighted J^T r share (1)
 };
 
 // Views of the batch-shared tables after they were copied into LDS.  Plain local structs whose
@@ -98,6 +99,14 @@ __host__ __device__ __forceinline__ int srcStrideFor(int nsrc) {
   return (x & 31) == 16 ? x : x + 16;
 }
 constexpr int kSrcCh = 15; // D(7) | A(7) | g share (the tree kernels; the one-launch solve keeps the g share in uy's place: 14)
+// The one-launch solve's slot tables are SLOT-major with a compile-time stride: D channels at 0..6, A channels at 7..13 of a
+// slot, so that every access is one per-slot address plus an immediate (a run-time channel stride cost fourteen SGPR bases
+// per term record, which spilled).  14 keeps the MFMA operand loads of phase G -- 16 slots x 2 adjacent channels per 32
+// lanes -- in 32 different banks (14 i mod 32 takes the sixteen even values); phase E's per-slot stores are two-way.
+constexpr int kSlotStride = 14;
+__host__ __device__ __forceinline__ size_t slotTableFloats(int nsrc) { // never more than (kSrcCh - 1) * srcStrideFor(nsrc)
+  return size_t(kSlotStride) * size_t((nsrc + 15) & ~15);
+}
 
 // ---------------------------------------------------------------------------------------------
 // adjoint machinery: sums over a joint's own units, then over its subtree (= a DFS index range)
