@@ -15,13 +15,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/mmx.h"
 #include "mmx_constraint_intake.hpp"
 
 namespace mmx {
 
-constexpr int kJs = 17; // floats per joint in js[]: t(3) q(4) s | axes (9); odd stride (lanes = joints read a field without LDS bank
+constexpr int kJs = 17; // floats (doubles in the double and mixed-precision solves) per joint in js[]: t(3) q(4) s | axes (9); odd stride (lanes = joints read a field without LDS bank
                       // conflicts).  21 until round 5: the four pad floats per joint were what stood between the one-launch solve and a
                       // fourth workgroup per CU (288 of the 180 floats it is under the 40 KB mark now)
 // Pivot threshold of every single-precision Cholesky in this library: when column j's pivot
@@ -71,67 +72,88 @@ constexpr float kFactorDamping = 1e-5f;
 constexpr float kPrecisionGain = 0.042f;
 constexpr float kPivotFloorOrOne = kPivotFloor > 0.f ? kPivotFloor : 1.f;
 
-constexpr float kLn2 = 0.693147180559945309417232121458176568f; // momentum/math/constants.h:30,40
+// momentum/math/constants.h:30,40
+template <class T>
+constexpr T kLn2T = T(0.693147180559945309417232121458176568);
+constexpr float kLn2 = kLn2T<float>;
 
-struct F3 {
-  float x, y, z;
+// Vectors and quaternions over the scalar T: float in the single-precision kernels, double in mmx_solve_f64 (mmx_f64.hip) and
+// in the mixed-precision one-launch solve (mmx_mixed.hpp).  Eigen's operation order throughout.
+template <class T>
+struct Vec3T {
+  using scalar = T;
+  T x, y, z;
 };
-struct Q4 { // Eigen storage order
-  float x, y, z, w;
+template <class T>
+struct QuatT { // Eigen storage order
+  T x, y, z, w;
 };
+using F3 = Vec3T<float>;
+using Q4 = QuatT<float>;
+using D3 = Vec3T<double>;
+using DQ = QuatT<double>;
 
 __device__ __forceinline__ F3 f3(float x, float y, float z) {
   return F3{x, y, z};
 }
-__device__ __forceinline__ F3 operator+(F3 a, F3 b) {
-  return F3{a.x + b.x, a.y + b.y, a.z + b.z};
+template <class T>
+__device__ __forceinline__ Vec3T<T> operator+(Vec3T<T> a, Vec3T<T> b) {
+  return Vec3T<T>{a.x + b.x, a.y + b.y, a.z + b.z};
 }
-__device__ __forceinline__ F3 operator-(F3 a, F3 b) {
-  return F3{a.x - b.x, a.y - b.y, a.z - b.z};
+template <class T>
+__device__ __forceinline__ Vec3T<T> operator-(Vec3T<T> a, Vec3T<T> b) {
+  return Vec3T<T>{a.x - b.x, a.y - b.y, a.z - b.z};
 }
-__device__ __forceinline__ F3 operator*(float s, F3 a) {
-  return F3{s * a.x, s * a.y, s * a.z};
+template <class T> // (the scalar is not deduced: it converts to the vector's type like an ordinary argument)
+__device__ __forceinline__ Vec3T<T> operator*(typename Vec3T<T>::scalar s, Vec3T<T> a) {
+  return Vec3T<T>{s * a.x, s * a.y, s * a.z};
 }
-__device__ __forceinline__ F3 cross(F3 a, F3 b) {
-  return F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+template <class T>
+__device__ __forceinline__ Vec3T<T> cross(Vec3T<T> a, Vec3T<T> b) {
+  return Vec3T<T>{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
-__device__ __forceinline__ float dot(F3 a, F3 b) {
+template <class T>
+__device__ __forceinline__ T dot(Vec3T<T> a, Vec3T<T> b) {
   return a.x * b.x + a.y * b.y + a.z * b.z;
 }
 // Eigen quaternion product
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  return Q4{
+template <class T>
+__device__ __forceinline__ QuatT<T> qmul(QuatT<T> a, QuatT<T> b) {
+  return QuatT<T>{
       a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
       a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z,
       a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x,
       a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
 }
 // Eigen _transformVector: v + w*uv + qv x uv, uv = 2 (qv x v)
-__device__ __forceinline__ F3 qrot(Q4 q, F3 v) {
-  const F3 qv{q.x, q.y, q.z};
-  F3 uv = cross(qv, v);
+template <class T>
+__device__ __forceinline__ Vec3T<T> qrot(QuatT<T> q, Vec3T<T> v) {
+  const Vec3T<T> qv{q.x, q.y, q.z};
+  Vec3T<T> uv = cross(qv, v);
   uv = uv + uv;
   return v + q.w * uv + cross(qv, uv);
 }
 // column c of Eigen toRotationMatrix
-__device__ __forceinline__ F3 qmatCol(Q4 q, int c) {
-  const float tx = 2.f * q.x, ty = 2.f * q.y, tz = 2.f * q.z;
-  const float twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-  const float txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-  const float tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+template <class T>
+__device__ __forceinline__ Vec3T<T> qmatCol(QuatT<T> q, int c) {
+  const T tx = T(2) * q.x, ty = T(2) * q.y, tz = T(2) * q.z;
+  const T twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+  const T txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
+  const T tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
   if (c == 0) {
-    return F3{1.f - (tyy + tzz), txy + twz, txz - twy};
+    return Vec3T<T>{T(1) - (tyy + tzz), txy + twz, txz - twy};
   }
   if (c == 1) {
-    return F3{txy - twz, 1.f - (txx + tzz), tyz + twx};
+    return Vec3T<T>{txy - twz, T(1) - (txx + tzz), tyz + twx};
   }
-  return F3{txz + twy, tyz - twx, 1.f - (txx + tyy)};
+  return Vec3T<T>{txz + twy, tyz - twx, T(1) - (txx + tyy)};
 }
-__device__ __forceinline__ Q4 qnormalized(Q4 q) { // Eigen normalized(): q / sqrt(|q|^2)
-  const float n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
-  if (n2 > 0.f) {
-    const float n = sqrtf(n2);
-    return Q4{q.x / n, q.y / n, q.z / n, q.w / n};
+template <class T>
+__device__ __forceinline__ QuatT<T> qnormalized(QuatT<T> q) { // Eigen normalized(): q / sqrt(|q|^2)
+  const T n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
+  if (n2 > T(0)) {
+    const T n = sqrt(n2);
+    return QuatT<T>{q.x / n, q.y / n, q.z / n, q.w / n};
   }
   return q;
 }
@@ -207,34 +229,47 @@ struct LossDev {
   float alpha, invC2;
   float c; // the scale as given (1 when none was): GeneralizedLossT<double> forms 1 / c^2 in double (mmx_f64.hip)
 };
-__device__ __forceinline__ float lossValue(const LossDev& l, float s) {
-  const float q = s * l.invC2;
+// 1 / c^2: the single-precision kernels take the host's float; GeneralizedLossT<double> forms it in double from the scale
+__device__ __forceinline__ float lossInvC2(const LossDev& l, float) {
+  return l.invC2;
+}
+__device__ __forceinline__ double lossInvC2(const LossDev& l, double) {
+  return 1.0 / (double(l.c) * double(l.c));
+}
+template <class T>
+__device__ __forceinline__ T lossValue(const LossDev& l, T s) { // generalized_loss.cpp:104-140
+  const T q = s * lossInvC2(l, T());
   switch (l.type) {
     case 0:
       return q;
     case 1:
-      return sqrtf(q + 1.f) - 1.f;
+      return sqrt(q + T(1)) - T(1);
     case 2:
-      return logf(0.5f * q + 1.f);
+      return log(T(0.5) * q + T(1));
     case 3:
-      return 1.f - expf(-0.5f * q);
-    default:
-      return (powf(q / fabsf(l.alpha - 2.f) + 1.f, 0.5f * l.alpha) - 1.f) * fabsf(l.alpha - 2.f) / l.alpha;
+      return T(1) - exp(T(-0.5) * q);
+    default: {
+      const T a = T(l.alpha);
+      return (pow(q / fabs(a - T(2)) + T(1), T(0.5) * a) - T(1)) * fabs(a - T(2)) / a;
+    }
   }
 }
-__device__ __forceinline__ float lossDeriv(const LossDev& l, float s) {
-  const float q = s * l.invC2;
+template <class T>
+__device__ __forceinline__ T lossDeriv(const LossDev& l, T s) {
+  const T ic = lossInvC2(l, T()), q = s * ic;
   switch (l.type) {
     case 0:
-      return l.invC2;
+      return ic;
     case 1:
-      return 0.5f * l.invC2 / sqrtf(q + 1.f);
+      return T(0.5) * ic / sqrt(q + T(1));
     case 2:
-      return l.invC2 / (l.invC2 * s + 2.f);
+      return ic / (ic * s + T(2));
     case 3:
-      return 0.5f * l.invC2 * expf(-0.5f * q);
-    default:
-      return 0.5f * l.invC2 * powf(q / fabsf(l.alpha - 2.f) + 1.f, 0.5f * l.alpha - 1.f);
+      return T(0.5) * ic * exp(T(-0.5) * q);
+    default: {
+      const T a = T(l.alpha);
+      return T(0.5) * ic * pow(q / fabs(a - T(2)) + T(1), T(0.5) * a - T(1));
+    }
   }
 }
 
@@ -703,8 +738,29 @@ __device__ __forceinline__ Unit evalUnit(const ProblemDev& pb, const float* js, 
   return evalUnitFrom(pb, loadUnitInput(pb, b, u), js, u);
 }
 
+// translationAxis column d of a joint = column d of parent.toLinear() = R(q_p) * s_p (joint_state.cpp:36-42); identity for a root.
+// Two overloads on purpose: the float one reads the parent's scale after its rotation, the double one before it.  One order for
+// both changes the instruction order of the single-precision kernels or the multiply-adds the compiler contracts in the
+// mixed-precision solve (its results then move in the last bits).
+__device__ __forceinline__ F3 transAxisCol(const float* js, int parent, int d) {
+  if (parent < 0) {
+    return F3{d == 0 ? 1.f : 0.f, d == 1 ? 1.f : 0.f, d == 2 ? 1.f : 0.f};
+  }
+  const float* p = js + kJs * parent;
+  const F3 c = qmatCol(Q4{p[3], p[4], p[5], p[6]}, d);
+  return F3{c.x * p[7], c.y * p[7], c.z * p[7]};
+}
+__device__ __forceinline__ D3 transAxisCol(const double* js, int parent, int d) {
+  if (parent < 0) {
+    return D3{d == 0 ? 1.0 : 0.0, d == 1 ? 1.0 : 0.0, d == 2 ? 1.0 : 0.0};
+  }
+  const double* p = js + kJs * parent;
+  return p[7] * qmatCol(DQ{p[3], p[4], p[5], p[6]}, d);
+}
+
 // d(unit vector)/d(joint-parameter row (a,dof)) for a source term of a column; the three
 // formulas of joint_error_function-inl.h:248-291 with joint_state.cpp:68-82.
+// (mmx_f64.hip keeps a double form of its own, sourceDerivativeF64, for the reason given at transAxisCol)
 __device__ __forceinline__ F3 sourceDerivative(const ColumnSourceDev& s, const float* js, const Unit& un, bool& applies) {
   const bool anc = (s.tin <= un.tin) && (un.tin < s.tout);
   const float* a = js + kJs * s.joint;
@@ -715,13 +771,8 @@ __device__ __forceinline__ F3 sourceDerivative(const ColumnSourceDev& s, const f
     return cross(F3{ax[0], ax[1], ax[2]}, off);
   }
   applies = anc && un.isPoint;
-  if (s.dof < 3) { // translation: column dof of parent.toLinear() = R(q_p) * s_p; identity for a root
-    if (s.parent < 0) {
-      return F3{s.dof == 0 ? 1.f : 0.f, s.dof == 1 ? 1.f : 0.f, s.dof == 2 ? 1.f : 0.f};
-    }
-    const float* p = js + kJs * s.parent;
-    const F3 c = qmatCol(Q4{p[3], p[4], p[5], p[6]}, s.dof);
-    return F3{c.x * p[7], c.y * p[7], c.z * p[7]};
+  if (s.dof < 3) { // translation
+    return transAxisCol(js, s.parent, s.dof);
   }
   return kLn2 * (un.v - F3{a[0], a[1], a[2]}); // scale: (v - t_a) * ln2
 }
@@ -755,24 +806,31 @@ __device__ __forceinline__ F3 pairSourceDerivative(const float* js, int joint, i
 // MMX_JC_JOINT_TO_JOINT_DISTANCE (pairPoint): v_n is a second POINT, on joint `joint2`, with its own ancestor chain; its
 // derivative dn = -dp, so the gather needs dp only (pairSourceDerivative).
 // ---------------------------------------------------------------------------------------------
-struct JointEval {
-  F3 vp, vn;
-  float dp[9], dn[9];
-  float f[3];
-  float sigma; // derivScale = sqrt(w * loss'(|f|^2)) ; 0 when the rows stay zero
-  float werr; // w * loss(|f|^2)
+// The record and normalizedOrSame serve float and double; evalJointConstraint / evalEllipsoid here are the float evaluation and
+// mmx_f64.hip has the double one (evalJointConstraintF64 / evalEllipsoidF64): instantiated from one text the double solve's
+// multiply-adds are contracted differently and its results move in the last bits.
+template <class T>
+struct JointEvalT {
+  Vec3T<T> vp, vn;
+  T dp[9], dn[9];
+  T f[3];
+  T sigma; // derivScale = sqrt(w * loss'(|f|^2)) ; 0 when the rows stay zero
+  T werr; // w * loss(|f|^2)
   int nrows;
   bool hasPoint, hasDir, pairPoint;
 };
+using JointEval = JointEvalT<float>;
 // flag word of a constraint record: rows | 16: point | 32: second vector | 64: the second vector is a point with its own
 // DFS position (stored where the ellipsoid records keep tinStop)
-__device__ __forceinline__ int jointEvalFlags(const JointEval& o) {
+template <class T>
+__device__ __forceinline__ int jointEvalFlags(const JointEvalT<T>& o) {
   return o.nrows | (o.hasPoint ? 16 : 0) | (o.hasDir ? 32 : 0) | (o.pairPoint ? 64 : 0);
 }
 
-__device__ __forceinline__ F3 normalizedOrSame(const F3& a) { // Eigen normalized(): unchanged when the norm is zero
-  const float n2 = dot(a, a);
-  return n2 > 0.f ? (1.f / sqrtf(n2)) * a : a;
+template <class T>
+__device__ __forceinline__ Vec3T<T> normalizedOrSame(const Vec3T<T>& a) { // Eigen normalized(): unchanged when the norm is zero
+  const T n2 = dot(a, a);
+  return n2 > T(0) ? (T(1) / sqrt(n2)) * a : a;
 }
 
 // (host twin: jointBlockRows in mmx_capi.hip)
@@ -934,10 +992,13 @@ __device__ __forceinline__ JointEval evalJointConstraint(const JointBlockDev& k,
 // computeEllipsoidError / the point and weights of computeEllipsoidJacobian
 // (momentum/character_solver/limit_error_function.cpp:173-195,702-737): position of the constrained
 // point, its offset from the projection onto the ellipsoid, jwgt = sqrt(tWeight * 1e-4 * weight).
-struct EllipsoidEval {
-  F3 position, diff;
-  float jwgt, werr;
+// tWeight: kLimitWeight * weight_ as the caller forms it (1e+1f * wLimit); a block with weight_ <= 0 is the caller's to skip.
+template <class T>
+struct EllipsoidEvalT {
+  Vec3T<T> position, diff;
+  T jwgt, werr;
 };
+using EllipsoidEval = EllipsoidEvalT<float>;
 __device__ __forceinline__ F3 affineApply(const float* a, const F3& p) { // 3 x 4 row-major
   return F3{a[0] * p.x + a[1] * p.y + a[2] * p.z + a[3], a[4] * p.x + a[5] * p.y + a[6] * p.z + a[7], a[8] * p.x + a[9] * p.y + a[10] * p.z + a[11]};
 }
@@ -1255,16 +1316,19 @@ __device__ __forceinline__ double waveReduceSum(double v) {
   return (row(0) + row(16)) + (row(32) + row(48));
 }
 
-// this thread's share of the blocks' error at the parameters `th`.  kJacobianRows: the value
-// getJacobian returns (model rows with weight <= 0 are skipped, model_parameters_error_function.cpp:113),
-// else the one getError returns (:54-58).
-template <bool kJacobianRows>
-__device__ __forceinline__ double paramRowsError(const RigDev& rig, const ProblemDev& pb, int P, const float* th, int b, int tid) {
+// this thread's share of the error of the parameter-space blocks at the parameters `th`: LimitErrorFunctionT<T> (the limit
+// types on model / joint parameters, limit_error_function.cpp:992-1122) and ModelParametersErrorFunctionT<T>
+// (model_parameters_error_function.cpp:44-131).  kJacobianRows: the value getJacobian returns (model rows with weight <= 0
+// are skipped, :113), else the one getError returns (:54-58).  T: float / double, the precision the rows are evaluated in;
+// TH: how theta is stored: T itself, or T in LDS (the address-space-qualified double of mmx_f64.hip).
+template <bool kJacobianRows, class T, class TH>
+__device__ __forceinline__ double paramRowsErrorT(const RigDev& rig, const ProblemDev& pb, int P, const TH* th, int b, int tid) {
+  static_assert(std::is_same<decltype(+th[0]), T>::value, "evalLimit reads theta through a T pointer");
   double e = 0.0;
   if (pb.NL > 0 && pb.wLimit > 0.f) {
-    const float tWeight = 1e+1f * pb.wLimit;
+    const T tWeight = T(1e+1f * pb.wLimit); // kLimitWeight * weight_ (a float product in both instantiations)
     for (int l = tid; l < pb.NL; l += 256) {
-      e += double(evalLimit(rig, pb.limits[l], th, pb.enabledMask, tWeight).err);
+      e += double(evalLimit<T>(rig, pb.limits[l], (const T*)th, pb.enabledMask, tWeight).err); // (cold path: generic pointer)
     }
   }
   if (pb.hasModel && pb.wModel > 0.f) {
@@ -1273,17 +1337,16 @@ __device__ __forceinline__ double paramRowsError(const RigDev& rig, const Proble
     double em = 0.0;
     for (int i = tid; i < P; i += 256) {
       if (pb.enabledMask[i] != 0) {
-        const float w = tw[i];
-        if (!kJacobianRows || w > 0.f) {
-          const float pd = w * (th[i] - tp[i]);
+        const T w = T(tw[i]);
+        if (!kJacobianRows || w > T(0)) {
+          const T pd = w * (T(th[i]) - T(tp[i]));
           em += double(pd * pd);
         }
       }
     }
-    e += em * double(pb.wModel) * double(1e-1f);
+    e += em * double(pb.wModel) * double(T(1e-1)); // kMotionWeight (T(1e-1), model_parameters_error_function.h:61)
   }
   return e;
 }
-
 
 } // namespace mmx

@@ -16,7 +16,6 @@
 // non-zeros per row go straight into H and g (the products J^T J would form from them, in double).  The further joint
 // error functions and ellipsoid limits are single-precision only (mmx_solve_f64 returns MMX_ERR_UNSUPPORTED for them).
 #include "mmx_device.hpp"
-#include "mmx_device_d.hpp"
 #include "mmx_kernels.hpp"
 
 #include <cfloat>
@@ -32,13 +31,11 @@ namespace {
 typedef __attribute__((address_space(3))) double ldsd;
 typedef __attribute__((address_space(3))) int ldsi;
 
-constexpr int kDs = 17; // doubles per joint: world t(3) q(4) s(1) | rotation axes x, y, z (9)
-
 struct F64Lds {
   ldsd* th; // [P]
   ldsd* trial; // [P]
   ldsd* jp; // [7 J]
-  ldsd* js; // [kDs J]
+  ldsd* js; // [kJs J]
   ldsd* uv; // [3 U] unit world vector
   ldsd* ur; // [M] scaled residual rows: 3 U of the position / orientation blocks, then the further joint error functions'
   ldsd* us; // [U] derivScale
@@ -49,7 +46,7 @@ struct F64Lds {
   ldsi* flags; // [4]
   ldsi* colOf; // [P] solve column of a model parameter, or -1
   ldsd* jl; // [n][rc + 1] a chunk of J's rows, column-major (normal equations)
-  ldsd* gev; // [G][kGevD] the further joint error functions' evaluations (JointEvalD, rows scaled by sigma)
+  ldsd* gev; // [G][kGevD] the further joint error functions' evaluations (JointEvalT<double>, rows scaled by sigma)
   // ---- the resident instantiation (kRes): the system never leaves LDS
   ldsd* H; // [n (n + 1) / 2] lower triangle of H, then of its factor, packed by columns (hpos)
   ldsd* invd; // [n] 1 / L(k,k)
@@ -88,10 +85,10 @@ __device__ void fkF64(const RigDev& rig, const F64Lds& s, const ldsd* th, int ti
     sincos(0.5 * p[4], &sy, &cy);
     sincos(0.5 * p[5], &sz, &cz);
     const DQ q0{double(pre[0]), double(pre[1]), double(pre[2]), double(pre[3])};
-    const DQ q1 = dqmul(q0, DQ{0.0, 0.0, sz, cz});
-    const DQ q2 = dqmul(q1, DQ{0.0, sy, 0.0, cy});
-    const DQ ql = dqmul(q2, DQ{sx, 0.0, 0.0, cx});
-    ldsd* o = s.js + kDs * j;
+    const DQ q1 = qmul(q0, DQ{0.0, 0.0, sz, cz});
+    const DQ q2 = qmul(q1, DQ{0.0, sy, 0.0, cy});
+    const DQ ql = qmul(q2, DQ{sx, 0.0, 0.0, cx});
+    ldsd* o = s.js + kJs * j;
     o[0] = double(off[0]) + p[0], o[1] = double(off[1]) + p[1], o[2] = double(off[2]) + p[2];
     o[3] = ql.x, o[4] = ql.y, o[5] = ql.z, o[6] = ql.w, o[7] = exp2(p[6]);
     o[8] = q1.x, o[9] = q1.y, o[10] = q1.z, o[11] = q1.w, o[12] = q2.x, o[13] = q2.y, o[14] = q2.z, o[15] = q2.w;
@@ -102,23 +99,23 @@ __device__ void fkF64(const RigDev& rig, const F64Lds& s, const ldsd* th, int ti
     for (int i = rig.levelStart[lvl] + tid; i < i1; i += 256) {
       const int j = rig.levelOrder[i];
       const float* pre = rig.preRot + 4 * j;
-      ldsd* o = s.js + kDs * j;
+      ldsd* o = s.js + kJs * j;
       const DQ q0{double(pre[0]), double(pre[1]), double(pre[2]), double(pre[3])};
       const DQ q1{o[8], o[9], o[10], o[11]}, q2{o[12], o[13], o[14], o[15]};
       DQ qp{0.0, 0.0, 0.0, 1.0};
       const int par = rig.parent[j];
       if (par >= 0) {
-        const ldsd* w = s.js + kDs * par;
+        const ldsd* w = s.js + kJs * par;
         const D3 tp{w[0], w[1], w[2]};
         qp = DQ{w[3], w[4], w[5], w[6]};
-        const D3 t = tp + dqrot(qp, w[7] * D3{o[0], o[1], o[2]}); // transform.h:124-129
-        const DQ q = dqmul(qp, DQ{o[3], o[4], o[5], o[6]});
+        const D3 t = tp + qrot(qp, w[7] * D3{o[0], o[1], o[2]}); // transform.h:124-129
+        const DQ q = qmul(qp, DQ{o[3], o[4], o[5], o[6]});
         o[0] = t.x, o[1] = t.y, o[2] = t.z, o[3] = q.x, o[4] = q.y, o[5] = q.z, o[6] = q.w, o[7] = w[7] * o[7];
       }
       if (withAxes) { // rotationAxis.col(i) = (q_parent * q_partial) * e_i (joint_state.cpp:53-54)
-        const D3 az = dqrot(dqmul(qp, q0), D3{0.0, 0.0, 1.0});
-        const D3 ay = dqrot(dqmul(qp, q1), D3{0.0, 1.0, 0.0});
-        const D3 ax = dqrot(dqmul(qp, q2), D3{1.0, 0.0, 0.0});
+        const D3 az = qrot(qmul(qp, q0), D3{0.0, 0.0, 1.0});
+        const D3 ay = qrot(qmul(qp, q1), D3{0.0, 1.0, 0.0});
+        const D3 ax = qrot(qmul(qp, q2), D3{1.0, 0.0, 0.0});
         o[8] = ax.x, o[9] = ax.y, o[10] = ax.z, o[11] = ay.x, o[12] = ay.y, o[13] = ay.z, o[14] = az.x, o[15] = az.y, o[16] = az.z;
       }
     }
@@ -131,7 +128,7 @@ __device__ void fkF64(const RigDev& rig, const F64Lds& s, const ldsd* th, int ti
 // for unit u of instance b; returns the unit's share of the error (w * loss(|f|^2), once per constraint).
 __device__ double evalUnitF64(const ProblemDev& pb, const F64Lds& s, int b, int u, bool store) {
   const UnitInput in = loadUnitInput(pb, b, u);
-  const ldsd* w = s.js + kDs * in.joint;
+  const ldsd* w = s.js + kJs * in.joint;
   const D3 t{w[0], w[1], w[2]};
   const DQ q{w[3], w[4], w[5], w[6]};
   const bool isPoint = u < pb.Kp;
@@ -140,21 +137,21 @@ __device__ double evalUnitF64(const ProblemDev& pb, const F64Lds& s, int b, int 
   bool first = true;
   const LossDev& ls = isPoint ? pb.lossPos : pb.lossOri;
   if (isPoint) {
-    v = t + dqrot(q, w[7] * D3{double(in.a[0]), double(in.a[1]), double(in.a[2])});
+    v = t + qrot(q, w[7] * D3{double(in.a[0]), double(in.a[1]), double(in.a[2])});
     f = v - D3{double(in.t[0]), double(in.t[1]), double(in.t[2])};
-    sqr = ddot(f, f);
+    sqr = dot(f, f);
     fw = double(pb.wPos);
   } else {
     const int uo = u - pb.Kp, k = uo - 3 * (uo / 3);
     // OrientationDataT<double>'s constructor normalises in double (orientation_error_function.h:33-35)
-    const DQ qo = dqnormalized(DQ{double(in.a[0]), double(in.a[1]), double(in.a[2]), double(in.a[3])});
-    const DQ qt = dqnormalized(DQ{double(in.t[0]), double(in.t[1]), double(in.t[2]), double(in.t[3])});
-    v = dqrot(q, dqmatCol(qo, k));
-    f = v - dqmatCol(qt, k);
+    const DQ qo = qnormalized(DQ{double(in.a[0]), double(in.a[1]), double(in.a[2]), double(in.a[3])});
+    const DQ qt = qnormalized(DQ{double(in.t[0]), double(in.t[1]), double(in.t[2]), double(in.t[3])});
+    v = qrot(q, qmatCol(qo, k));
+    f = v - qmatCol(qt, k);
     sqr = 0.0;
     for (int kk = 0; kk < 3; ++kk) { // the loss sees all nine rows of the constraint
-      const D3 fo = dqrot(q, dqmatCol(qo, kk)) - dqmatCol(qt, kk);
-      sqr += ddot(fo, fo);
+      const D3 fo = qrot(q, qmatCol(qo, kk)) - qmatCol(qt, kk);
+      sqr += dot(fo, fo);
     }
     first = k == 0;
     fw = double(pb.wOri);
@@ -162,8 +159,8 @@ __device__ double evalUnitF64(const ProblemDev& pb, const F64Lds& s, int b, int 
   double sigma = 0.0, werr = 0.0;
   if (in.cw != 0.f && fw > 0.0) {
     const double wgt = double(in.cw) * fw;
-    werr = first ? wgt * dlossValue(ls, sqr) : 0.0;
-    sigma = sqrt(wgt * dlossDeriv(ls, sqr));
+    werr = first ? wgt * lossValue(ls, sqr) : 0.0;
+    sigma = sqrt(wgt * lossDeriv(ls, sqr));
   }
   if (store) {
     s.uv[3 * u] = v.x, s.uv[3 * u + 1] = v.y, s.uv[3 * u + 2] = v.z;
@@ -186,58 +183,16 @@ __device__ double blockSumF64(const F64Lds& s, double v, int tid) {
   return (s.red[0] + s.red[1]) + (s.red[2] + s.red[3]);
 }
 
-// this thread's share of the error of the parameter-space blocks at `th`: LimitErrorFunctionT<double> (the limit types
-// on model / joint parameters, limit_error_function.cpp:992-1122) and ModelParametersErrorFunctionT<double>
-// (model_parameters_error_function.cpp:44-131).  kJacobianRows: the value getJacobian returns (model rows with weight
-// <= 0 are skipped, :113), else the one getError returns (:54-58).
-template <bool kJacobianRows>
-__device__ double paramRowsErrorF64(const RigDev& rig, const ProblemDev& pb, const ldsd* th, int b, int tid) {
-  double e = 0.0;
-  if (pb.NL > 0 && pb.wLimit > 0.f) {
-    const double tWeight = double(1e+1f * pb.wLimit); // kLimitWeight * weight_ (a float product in both instantiations)
-    for (int l = tid; l < pb.NL; l += 256) {
-      e += evalLimit<double>(rig, pb.limits[l], (const double*)th, pb.enabledMask, tWeight).err; // (cold path: generic pointer)
-    }
-  }
-  if (pb.hasModel && pb.wModel > 0.f) {
-    const float* tp = pb.mpTarget + size_t(b) * rig.P;
-    const float* tw = pb.mpWeights + size_t(b) * rig.P;
-    double em = 0.0;
-    for (int i = tid; i < rig.P; i += 256) {
-      if (pb.enabledMask[i] != 0) {
-        const double w = double(tw[i]);
-        if (!kJacobianRows || w > 0.0) {
-          const double pd = w * (th[i] - double(tp[i]));
-          em += pd * pd;
-        }
-      }
-    }
-    e += em * double(pb.wModel) * 1e-1; // kMotionWeight (T(1e-1), model_parameters_error_function.h:61)
-  }
-  return e;
-}
-
 // SkeletonSolverFunctionT<double>::getError (skeleton_solver_function.cpp:64-83; rounded through float, :82)
 // The further JointErrorFunctionT<double> specialisations (Plane / HalfPlane, AimDist / AimDir, FixedAxisDiff / Cos /
-// Angle, Normal, Projection, Distance, JointToJointDistance): evalFunction + the weighting of getJacobian in double -- evalJointConstraint of mmx_device.hpp with T =
-// double (the constraint data stay float like the reference's tensors; joint_error_function-inl.h:197-226).
-struct JointEvalD {
-  D3 vp, vn;
-  double dp[9], dn[9];
-  double f[3];
-  double sigma, werr;
-  int nrows;
-  bool hasPoint, hasDir, pairPoint; // pairPoint: vn is a second point on joint2 (MMX_JC_JOINT_TO_JOINT_DISTANCE), dn = -dp
-};
+// Angle, Normal, Projection, Distance, JointToJointDistance): evalFunction + the weighting of getJacobian in double (the constraint data stay float like the
+// reference's tensors; joint_error_function-inl.h:197-226).  evalJointConstraint of mmx_device.hpp in double, and a function
+// of its own, like evalEllipsoidF64 and sourceDerivativeF64 below: instantiated from one text with the float ones the
+// compiler contracts other multiply-adds, and the double solve's results move in the last bits.
 constexpr int kGevD = 26; // doubles per constraint in LDS: vp(3) vn(3) sigma dp(9) sigma dn(9) | tin, row | flags, tinStop (pair constraints: the second point's tin)
 
-__device__ __forceinline__ D3 dnormalizedOrSame(D3 a) { // Eigen normalized(): unchanged when the norm is zero
-  const double n2 = ddot(a, a);
-  return n2 > 0.0 ? (1.0 / sqrt(n2)) * a : a;
-}
-
-__device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd* js, int joint, int joint2, size_t c) {
-  JointEvalD o;
+__device__ JointEvalT<double> evalJointConstraintF64(const JointBlockDev& k, const ldsd* js, int joint, int joint2, size_t c) {
+  JointEvalT<double> o;
   o.vp = o.vn = D3{0.0, 0.0, 0.0};
   for (int i = 0; i < 9; ++i) {
     o.dp[i] = o.dn[i] = 0.0;
@@ -249,7 +204,7 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
   o.hasDir = k.type != MMX_JC_PLANE && k.type != MMX_JC_HALF_PLANE && k.type != MMX_JC_PROJECTION && k.type != MMX_JC_DISTANCE;
   o.pairPoint = k.type == MMX_JC_JOINT_TO_JOINT_DISTANCE;
   bool skip = false; // a projection behind the near plane: no error, rows zero
-  const ldsd* w = js + kDs * joint;
+  const ldsd* w = js + kJs * joint;
   const D3 t{w[0], w[1], w[2]};
   const DQ q{w[3], w[4], w[5], w[6]};
   const double sc = w[7];
@@ -262,19 +217,19 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
   };
   const D3 gl = o.pairPoint ? D3{0.0, 0.0, 0.0} : vec(k.global); // (the pair type has no world-space payload)
   if (o.hasPoint) {
-    o.vp = t + dqrot(q, sc * vec(k.localPoint)); // state.transform * point
+    o.vp = t + qrot(q, sc * vec(k.localPoint)); // state.transform * point
   }
   if (o.pairPoint) {
-    const ldsd* w2 = js + kDs * joint2;
-    o.vn = D3{w2[0], w2[1], w2[2]} + dqrot(DQ{w2[3], w2[4], w2[5], w2[6]}, w2[7] * vec(k.localDir)); // the second joint's transform * its point
+    const ldsd* w2 = js + kJs * joint2;
+    o.vn = D3{w2[0], w2[1], w2[2]} + qrot(DQ{w2[3], w2[4], w2[5], w2[6]}, w2[7] * vec(k.localDir)); // the second joint's transform * its point
   } else if (o.hasDir) {
-    o.vn = dqrot(q, dnormalizedOrSame(vec(k.localDir))); // state.rotation() * dir, normalised by the data ctor
+    o.vn = qrot(q, normalizedOrSame(vec(k.localDir))); // state.rotation() * dir, normalised by the data ctor
   }
   switch (k.type) {
     case MMX_JC_PLANE:
     case MMX_JC_HALF_PLANE: { // plane_error_function.cpp:52-71
-      const D3 nrm = dnormalizedOrSame(gl);
-      double val = ddot(o.vp, nrm) - double(k.planeD[c]);
+      const D3 nrm = normalizedOrSame(gl);
+      double val = dot(o.vp, nrm) - double(k.planeD[c]);
       const bool half = k.type == MMX_JC_HALF_PLANE;
       if (half && val > 0.0) {
         val = 0.0;
@@ -287,7 +242,7 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
     }
     case MMX_JC_AIM_DIST: { // aim_error_function.cpp:15-36
       const D3 tgt = gl - o.vp;
-      const double proj = ddot(o.vn, tgt);
+      const double proj = dot(o.vn, tgt);
       const D3 r = proj * o.vn - tgt;
       o.f[0] = r.x, o.f[1] = r.y, o.f[2] = r.z;
       o.dp[0] = o.dp[4] = o.dp[8] = 1.0;
@@ -298,7 +253,7 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
     }
     case MMX_JC_AIM_DIR: { // aim_error_function.cpp:39-67
       const D3 tgt = gl - o.vp;
-      const double nrm = sqrt(ddot(tgt, tgt));
+      const double nrm = sqrt(dot(tgt, tgt));
       D3 dir{0.0, 0.0, 0.0};
       if (nrm > 1e-16) {
         dir = (1.0 / nrm) * tgt;
@@ -311,20 +266,20 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
       break;
     }
     case MMX_JC_FIXED_AXIS_DIFF: { // fixed_axis_error_function.cpp:15-26
-      const D3 r = o.vn - dnormalizedOrSame(gl);
+      const D3 r = o.vn - normalizedOrSame(gl);
       o.f[0] = r.x, o.f[1] = r.y, o.f[2] = r.z;
       o.dn[0] = o.dn[4] = o.dn[8] = 1.0;
       break;
     }
     case MMX_JC_FIXED_AXIS_COS: { // :28-39
-      const D3 ga = dnormalizedOrSame(gl);
-      o.f[0] = 1.0 - ddot(o.vn, ga);
+      const D3 ga = normalizedOrSame(gl);
+      o.f[0] = 1.0 - dot(o.vn, ga);
       setRow(o.dn, ga, -1.0);
       break;
     }
     case MMX_JC_FIXED_AXIS_ANGLE: { // :41-66
-      const D3 ga = dnormalizedOrSame(gl);
-      const double d = ddot(o.vn, ga);
+      const D3 ga = normalizedOrSame(gl);
+      const double d = dot(o.vn, ga);
       o.f[0] = acos(fmin(fmax(d, -1.0), 1.0));
       const double sine = sqrt(1.0 - d * d);
       if (sine > 1e-9) {
@@ -335,13 +290,13 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
     case MMX_JC_PROJECTION: { // p = A x + a ; f = p.xy / p.z - (u, v) ; df/dx = (1 / p.z) [A_0 - f_x A_2 ; A_1 - f_y A_2]
       const float* m = k.projection + 12 * c;
       const D3 a0{m[0], m[1], m[2]}, a1{m[4], m[5], m[6]}, a2{m[8], m[9], m[10]};
-      const double pz = ddot(a2, o.vp) + double(m[11]);
+      const double pz = dot(a2, o.vp) + double(m[11]);
       if (pz < double(k.nearClip)) {
         skip = true;
         break;
       }
       const double iz = 1.0 / pz;
-      const double px = (ddot(a0, o.vp) + double(m[3])) * iz, py = (ddot(a1, o.vp) + double(m[7])) * iz;
+      const double px = (dot(a0, o.vp) + double(m[3])) * iz, py = (dot(a1, o.vp) + double(m[7])) * iz;
       o.f[0] = px - gl.x, o.f[1] = py - gl.y;
       setRow(o.dp, a0 - px * a2, iz);
       setRow(o.dp + 3, a1 - py * a2, iz);
@@ -349,7 +304,7 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
     }
     case MMX_JC_DISTANCE: { // f = |x - origin| - d ; df/dx = (x - origin)^T / |x - origin|
       const D3 diff = o.vp - gl;
-      const double nrm = sqrt(ddot(diff, diff));
+      const double nrm = sqrt(dot(diff, diff));
       o.f[0] = nrm - double(k.planeD[c]);
       if (nrm > 0.0) {
         setRow(o.dp, diff, 1.0 / nrm);
@@ -358,8 +313,8 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
     }
     case MMX_JC_JOINT_TO_JOINT_DISTANCE: { // f = |x_a - x_b| - d ; df/dx_a = n^T = -df/dx_b, n = (x_a - x_b) / |x_a - x_b|
       // (two points of ONE joint: s R (o_a - o_b), exactly zero for equal offsets -- see evalJointConstraint)
-      const D3 diff = joint2 == joint ? dqrot(q, sc * (vec(k.localPoint) - vec(k.localDir))) : o.vp - o.vn;
-      const double nrm = sqrt(ddot(diff, diff));
+      const D3 diff = joint2 == joint ? qrot(q, sc * (vec(k.localPoint) - vec(k.localDir))) : o.vp - o.vn;
+      const double nrm = sqrt(dot(diff, diff));
       o.f[0] = nrm - double(k.planeD[c]);
       if (nrm > 0.0) {
         setRow(o.dp, diff, 1.0 / nrm);
@@ -369,7 +324,7 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
     }
     default: { // MMX_JC_NORMAL, normal_error_function.cpp:14-31
       const D3 dist = o.vp - gl;
-      o.f[0] = ddot(o.vn, dist);
+      o.f[0] = dot(o.vn, dist);
       setRow(o.dp, o.vn, 1.0);
       setRow(o.dn, dist, 1.0);
       break;
@@ -379,21 +334,17 @@ __device__ JointEvalD evalJointConstraintF64(const JointBlockDev& k, const ldsd*
   if (!skip && cw != 0.0 && k.fw > 0.f) { // :197-199 ; blocks with weight_ <= 0 are skipped (skeleton_solver_function.cpp:223-231)
     const double sqr = o.f[0] * o.f[0] + o.f[1] * o.f[1] + o.f[2] * o.f[2];
     const double wgt = cw * double(k.fw);
-    o.werr = wgt * dlossValue(k.loss, sqr); // :207
-    o.sigma = sqrt(wgt * dlossDeriv(k.loss, sqr)); // :208
+    o.werr = wgt * lossValue(k.loss, sqr); // :207
+    o.sigma = sqrt(wgt * lossDeriv(k.loss, sqr)); // :208
   }
   return o;
 }
 
 // computeEllipsoidError / the point and weight of computeEllipsoidJacobian in double (evalEllipsoid of mmx_device.hpp;
 // limit_error_function.cpp:173-195,702-737)
-struct EllipsoidEvalD {
-  D3 position, diff;
-  double jwgt, werr;
-};
-__device__ EllipsoidEvalD evalEllipsoidF64(const EllipsoidDev& ct, const ldsd* js, float wLimit) {
-  const ldsd* wp = js + kDs * ct.parent;
-  const ldsd* we = js + kDs * ct.ellipsoidParent;
+__device__ EllipsoidEvalT<double> evalEllipsoidF64(const EllipsoidDev& ct, const ldsd* js, float wLimit) {
+  const ldsd* wp = js + kJs * ct.parent;
+  const ldsd* we = js + kJs * ct.ellipsoidParent;
   const D3 te{we[0], we[1], we[2]};
   const DQ qe{we[3], we[4], we[5], we[6]};
   auto affine = [](const float* a, D3 p) { // 3 x 4 row-major
@@ -402,16 +353,16 @@ __device__ EllipsoidEvalD evalEllipsoidF64(const EllipsoidDev& ct, const ldsd* j
         double(a[4]) * p.x + double(a[5]) * p.y + double(a[6]) * p.z + double(a[7]),
         double(a[8]) * p.x + double(a[9]) * p.y + double(a[10]) * p.z + double(a[11])};
   };
-  EllipsoidEvalD o;
-  o.position = D3{wp[0], wp[1], wp[2]} + dqrot(DQ{wp[3], wp[4], wp[5], wp[6]}, wp[7] * D3{double(ct.offset[0]), double(ct.offset[1]), double(ct.offset[2])});
-  const D3 local = (1.0 / we[7]) * dqrot(DQ{-qe.x, -qe.y, -qe.z, qe.w}, o.position - te); // transform.inverse() * position
-  const D3 nrm = dnormalizedOrSame(affine(ct.ellipsoidInv, local));
+  EllipsoidEvalT<double> o;
+  o.position = D3{wp[0], wp[1], wp[2]} + qrot(DQ{wp[3], wp[4], wp[5], wp[6]}, wp[7] * D3{double(ct.offset[0]), double(ct.offset[1]), double(ct.offset[2])});
+  const D3 local = (1.0 / we[7]) * qrot(DQ{-qe.x, -qe.y, -qe.z, qe.w}, o.position - te); // transform.inverse() * position
+  const D3 nrm = normalizedOrSame(affine(ct.ellipsoidInv, local));
   const D3 proj = affine(ct.ellipsoid, nrm);
-  o.diff = o.position - (te + dqrot(qe, we[7] * proj));
+  o.diff = o.position - (te + qrot(qe, we[7] * proj));
   o.jwgt = o.werr = 0.0;
   if (wLimit > 0.f) { // a block with weight_ <= 0 is skipped; its rows stay zero
     const double w = (10.0 * double(wLimit)) * double(1e-4f) * double(ct.weight); // kLimitWeight * weight_ * kPositionWeight * limit.weight
-    o.werr = w * ddot(o.diff, o.diff);
+    o.werr = w * dot(o.diff, o.diff);
     o.jwgt = sqrt(w);
   }
   return o;
@@ -436,7 +387,7 @@ __device__ double errorF64(const RigDev& rig, const ProblemDev& pb, const F64Lds
   for (int u = tid; u < pb.U; u += 256) {
     e += evalUnitF64(pb, s, b, u, false);
   }
-  e += paramRowsErrorF64<false>(rig, pb, th, b, tid);
+  e += paramRowsErrorT<false, double>(rig, pb, rig.P, th, b, tid);
   e += jointBlocksErrorF64(pb, s, b, tid);
   return double(float(blockSumF64(s, e, tid)));
 }
@@ -444,21 +395,21 @@ __device__ double errorF64(const RigDev& rig, const ProblemDev& pb, const F64Lds
 // d(unit vector) / d(joint parameter (joint, dof)) (joint_error_function-inl.h:248-291, joint_state.cpp:68-82)
 __device__ __forceinline__ D3 sourceDerivativeF64(const ColumnSourceDev& c, const ldsd* js, D3 v, int utin, bool isPoint, bool& applies) {
   const bool anc = c.tin <= utin && utin < c.tout;
-  const ldsd* a = js + kDs * c.joint;
+  const ldsd* a = js + kJs * c.joint;
   if (c.dof >= 3 && c.dof < 6) {
     const ldsd* ax = a + 8 + 3 * (c.dof - 3);
     applies = anc;
-    return dcross(D3{ax[0], ax[1], ax[2]}, isPoint ? v - D3{a[0], a[1], a[2]} : v);
+    return cross(D3{ax[0], ax[1], ax[2]}, isPoint ? v - D3{a[0], a[1], a[2]} : v);
   }
   applies = anc && isPoint;
   if (c.dof < 3) {
     if (c.parent < 0) {
       return D3{c.dof == 0 ? 1.0 : 0.0, c.dof == 1 ? 1.0 : 0.0, c.dof == 2 ? 1.0 : 0.0};
     }
-    const ldsd* p = js + kDs * c.parent;
-    return p[7] * dqmatCol(DQ{p[3], p[4], p[5], p[6]}, c.dof);
+    const ldsd* p = js + kJs * c.parent;
+    return p[7] * qmatCol(DQ{p[3], p[4], p[5], p[6]}, c.dof);
   }
-  return 0.693147180559945309417232121458176568 * (v - D3{a[0], a[1], a[2]});
+  return kLn2T<double> * (v - D3{a[0], a[1], a[2]});
 }
 
 // ---- the resident instantiation's three hot routines, each compiled on its own (not inlined: inside the kernel, whose
@@ -1037,7 +988,7 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
       p += (c + 1) & ~size_t(1);
       return r;
     };
-    s.th = take(P), s.trial = take(P), s.jp = take(7 * size_t(J)), s.js = take(size_t(kDs) * J);
+    s.th = take(P), s.trial = take(P), s.jp = take(7 * size_t(J)), s.js = take(size_t(kJs) * J);
     s.uv = take(3 * size_t(U)), s.ur = take(size_t(M)), s.us = take(U);
     s.g = take(n), s.d = take(n), s.red = take(8);
     s.utin = reinterpret_cast<ldsi*>(take((U + 1) / 2 + 1));
@@ -1139,12 +1090,12 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
       e += evalUnitF64(pb, s, b, u, true);
     }
     if (hasParamRows) {
-      e += paramRowsErrorF64<true>(rig, pb, s.th, b, tid);
+      e += paramRowsErrorT<true, double>(rig, pb, rig.P, s.th, b, tid);
     }
     for (int g = tid; g < G; g += 256) { // the further joint error functions: residual rows, evaluation record for the Jacobian
       const JointBlockDev k = jointBlockOf(pb, b, pb.genBlock[g]);
       const int i = g - k.first;
-      const JointEvalD o = evalJointConstraintF64(k, s.js, pb.genJoint[g], jointBlockSecondJoint(pb, k, g), size_t(b) * size_t(k.count) + size_t(i));
+      const JointEvalT<double> o = evalJointConstraintF64(k, s.js, pb.genJoint[g], jointBlockSecondJoint(pb, k, g), size_t(b) * size_t(k.count) + size_t(i));
       const int row = k.rowStart + o.nrows * i;
       e += o.werr;
       for (int q = 0; q < o.nrows; ++q) {
@@ -1163,7 +1114,7 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
     }
     for (int q = tid; q < pb.NE; q += 256) { // ellipsoid limits: a point constraint whose walk stops at ellipsoidParent
       const EllipsoidDev ct = pb.ellipsoids[q];
-      const EllipsoidEvalD o = evalEllipsoidF64(ct, s.js, pb.wLimit);
+      const EllipsoidEvalT<double> o = evalEllipsoidF64(ct, s.js, pb.wLimit);
       const int row = pb.rowsJoint - 3 * pb.NE + 3 * q;
       e += o.werr;
       s.ur[row] = o.diff.x * o.jwgt, s.ur[row + 1] = o.diff.y * o.jwgt, s.ur[row + 2] = o.diff.z * o.jwgt;
@@ -1866,7 +1817,7 @@ __global__ void __launch_bounds__(256) selectSuspectKernel(const int32_t* __rest
 
 static size_t solveF64BaseDoubles(int J, int P, int U, int n, int G, int genRows) {
   auto e = [](size_t c) { return (c + 1) & ~size_t(1); };
-  return 2 * e(P) + e(7 * size_t(J)) + e(size_t(kDs) * J) + e(3 * size_t(U)) + e(3 * size_t(U) + size_t(genRows)) + e(U) + 2 * e(n) + e(8) +
+  return 2 * e(P) + e(7 * size_t(J)) + e(size_t(kJs) * J) + e(3 * size_t(U)) + e(3 * size_t(U) + size_t(genRows)) + e(U) + 2 * e(n) + e(8) +
       e((U + 1) / 2 + 1) + e(2) + e((size_t(P) + 1) / 2) + e(size_t(kGevD) * size_t(G));
 }
 // rows of J staged per chunk: as many as fit next to the fixed part (at most 64, at least 4), leaving room for two

@@ -89,7 +89,7 @@ __device__ __forceinline__ void blockFkD(const RigView& rig, const MixLds& m, co
   __syncthreads();
   double loc[8];
   const int j = tid;
-  double* slot = m.js + kJsD * (j < rig.J ? j : 0);
+  double* slot = m.js + kJs * (j < rig.J ? j : 0);
   if (j < rig.J) {
     fkLocalFromParamsD(m.X + 7 * j, rig.preRot + 4 * j, rig.offset + 3 * j, loc, slot + 8);
     if (myLevel == 0) {
@@ -102,10 +102,10 @@ __device__ __forceinline__ void blockFkD(const RigView& rig, const MixLds& m, co
   __syncthreads();
   for (int lvl = 1; lvl < rig.numLevels; ++lvl) {
     if (j < rig.J && myLevel == lvl) {
-      const double* w = m.js + kJsD * rig.parent[j];
+      const double* w = m.js + kJs * rig.parent[j];
       const DQ qp{w[3], w[4], w[5], w[6]};
-      const D3 t = D3{w[0], w[1], w[2]} + dqrot(qp, w[7] * D3{loc[0], loc[1], loc[2]}); // transform.h:124-129
-      const DQ q = dqmul(qp, DQ{loc[3], loc[4], loc[5], loc[6]});
+      const D3 t = D3{w[0], w[1], w[2]} + qrot(qp, w[7] * D3{loc[0], loc[1], loc[2]}); // transform.h:124-129
+      const DQ q = qmul(qp, DQ{loc[3], loc[4], loc[5], loc[6]});
       slot[0] = t.x, slot[1] = t.y, slot[2] = t.z, slot[3] = q.x, slot[4] = q.y, slot[5] = q.z, slot[6] = q.w, slot[7] = w[7] * loc[7];
     }
     __syncthreads();
@@ -144,7 +144,7 @@ __device__ __forceinline__ double blockErrorD(
   blockFkD(rig, m, th, tid, myLevel, kStore, regRec);
   double e = mixUnits<kStore>(pb, s, m, b, U, tid);
   if (hasRows) {
-    e += paramRowsErrorD<false>(*rowsRig, pb, rig.P, th, b, tid);
+    e += paramRowsErrorT<false, double>(*rowsRig, pb, rig.P, th, b, tid);
   }
   const double tot = blockSumD(s.red, e, tid);
   if (unrounded != nullptr) {
@@ -168,12 +168,12 @@ __device__ __forceinline__ void mixAdjoint(const FV& fd, const FusedLds& s, cons
     for (int u = tid; u < fd.U; u += 256) {
       const D3 pu{m.up[3 * u], m.up[3 * u + 1], m.up[3 * u + 2]};
       const D3 y = yOf(u, fd.unitPos[u], pu);
-      const D3 Nv = dcross(pu, y); // points and directions share the channel (jt_times)
+      const D3 Nv = cross(pu, y); // points and directions share the channel (jt_times)
       const bool point = u < fd.Kp;
       double* o = m.X + 7 * u;
       o[0] = point ? y.x : 0.0, o[1] = point ? y.y : 0.0, o[2] = point ? y.z : 0.0;
       o[3] = Nv.x, o[4] = Nv.y, o[5] = Nv.z;
-      o[6] = point ? ddot(pu, y) : 0.0;
+      o[6] = point ? dot(pu, y) : 0.0;
     }
     __syncthreads();
     for (int item = tid; item < 7 * fd.numLoaded; item += 256) {
@@ -207,10 +207,10 @@ __device__ __forceinline__ void mixAdjoint(const FV& fd, const FusedLds& s, cons
         const int u = fd.posUnits[e];
         const D3 pu{m.up[3 * u], m.up[3 * u + 1], m.up[3 * u + 2]};
         const D3 y = yOf(u, k, pu);
-        Nv = Nv + dcross(pu, y);
+        Nv = Nv + cross(pu, y);
         if (u < fd.Kp) {
           Fv = Fv + y;
-          Dd += ddot(pu, y);
+          Dd += dot(pu, y);
         }
       }
       double* o = m.X + 7 * li;
@@ -231,7 +231,7 @@ __device__ __forceinline__ void mixAdjoint(const FV& fd, const FusedLds& s, cons
   __syncthreads();
   for (int e = tid; e < nsrc; e += 256) {
     const int info = s.mInfo[e];
-    slot[e] = double(s.mW[e]) * sourceGradientD(info & 0xfff, (info >> 12) & 7, (info >> 16) - 1, m.js, sub + 7 * (s.mTin[e] & 0xffff));
+    slot[e] = double(s.mW[e]) * sourceGradientT(info & 0xfff, (info >> 12) & 7, (info >> 16) - 1, m.js, sub + 7 * (s.mTin[e] & 0xffff));
   }
   __syncthreads();
   for (int c = tid; c < NP; c += 256) {
@@ -258,16 +258,16 @@ __device__ __forceinline__ void mixTangent(const RigView& rig, const FV& fd, con
   int target = -1;
   if (tid < J) {
     const int q = fd.dfsJoint[tid];
-    const double* ja = m.js + kJsD * q;
+    const double* ja = m.js + kJs * q;
     const double* d = m.X + 7 * q;
     const D3 ta{ja[0], ja[1], ja[2]};
     D3 Tv{0.0, 0.0, 0.0};
     if (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0) {
       const int par = rig.parent[q];
-      Tv = d[0] * transAxisColD(m.js, par, 0) + d[1] * transAxisColD(m.js, par, 1) + d[2] * transAxisColD(m.js, par, 2);
+      Tv = d[0] * transAxisCol(m.js, par, 0) + d[1] * transAxisCol(m.js, par, 1) + d[2] * transAxisCol(m.js, par, 2);
     }
     const D3 Om = d[3] * D3{ja[8], ja[9], ja[10]} + d[4] * D3{ja[11], ja[12], ja[13]} + d[5] * D3{ja[14], ja[15], ja[16]};
-    const D3 C = Tv - dcross(Om, ta) - (kLn2D * d[6]) * ta;
+    const D3 C = Tv - cross(Om, ta) - (kLn2T<double> * d[6]) * ta;
     acc[0] = C.x, acc[1] = C.y, acc[2] = C.z, acc[3] = Om.x, acc[4] = Om.y, acc[5] = Om.z, acc[6] = d[6];
     target = parentPos[tid];
     double* o = m.Y + kTanD * tid;
@@ -317,9 +317,9 @@ __device__ __forceinline__ void mixApply(
       fd, s, m, J, NP, n, nsrc, tid,
       [&](int u, int k, const D3& pu) {
         const double* pre = m.Y + kTanD * k;
-        D3 v = dcross(D3{pre[3], pre[4], pre[5]}, pu);
+        D3 v = cross(D3{pre[3], pre[4], pre[5]}, pu);
         if (u < fd.Kp) {
-          v = D3{pre[0], pre[1], pre[2]} + v + (kLn2D * pre[6]) * pu;
+          v = D3{pre[0], pre[1], pre[2]} + v + (kLn2T<double> * pre[6]) * pu;
         }
         const double sg = m.us[u];
         return (sg * sg) * v;
@@ -571,7 +571,7 @@ __device__ __forceinline__ double blockError(
     e += double(un.werr);
   }
   if (pb.M > pb.rowsJoint) {
-    e += paramRowsError<false>(rigDev, pb, rig.P, th, b, tid);
+    e += paramRowsErrorT<false, float>(rigDev, pb, rig.P, th, b, tid);
   }
   if (kGen) {
     e += generalRowsError(pb, s.js, b, tid);
@@ -1218,7 +1218,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     if (kMix) { // the double arrays, behind everything else (every offset so far is a multiple of 16 bytes)
       double* d = reinterpret_cast<double*>(smem + (lay.total - alignUp4(2 * mixPersistentDoubles(JL, P, U, NP))));
       m.th = d, d += P;
-      m.js = d, d += size_t(kJsD) * JL;
+      m.js = d, d += size_t(kJs) * JL;
       m.up = d, d += 3 * size_t(U);
       m.uf = d, d += 3 * size_t(U);
       m.us = d, d += U;
@@ -1434,7 +1434,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       blockFkD(rv, m, m.th, tid, mixLevel, true, mixRecP);
       double e = mixUnits<true>(pb, s, m, b, U, tid);
       if (hasParamRows) {
-        e += paramRowsErrorD<true>(rig, pb, P, m.th, b, tid);
+        e += paramRowsErrorT<true, double>(rig, pb, P, m.th, b, tid);
       }
       e = waveReduceSum(e);
       if (lane == 0) {
@@ -1460,7 +1460,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
         e += double(un.werr);
       }
       if (hasParamRows) {
-        e += paramRowsError<true>(rig, pb, P, s.th, b, tid);
+        e += paramRowsErrorT<true, float>(rig, pb, P, s.th, b, tid);
       }
       if (kGen) { // the further joint error functions and the ellipsoid limits: records for the rows of J_g, residual rows
         e += generalRowsEvaluate(pb, s.js, b, U, tid, s.gEv, s.gRes);
@@ -1540,7 +1540,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       }
       float jaMix[kJs]; // kMix: the slot's joint state rounded to single precision (H is the preconditioner)
       if (kMix) {
-        const double* ad = m.js + kJsD * cs.joint;
+        const double* ad = m.js + kJs * cs.joint;
 #pragma unroll
         for (int q = 0; q < kJs; ++q) {
           jaMix[q] = float(ad[q]);
@@ -1555,7 +1555,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       float bs = 0.f, tr;
       if (cs.dof < 3) {
         if (kMix) {
-          const D3 ad = transAxisColD(m.js, cs.parent, cs.dof);
+          const D3 ad = transAxisCol(m.js, cs.parent, cs.dof);
           al = F3{float(ad.x), float(ad.y), float(ad.z)};
         } else {
           al = transAxisCol(s.js, cs.parent, cs.dof);
@@ -1597,7 +1597,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
         d[q] = tv[q];
       }
       if (!kMix) {
-        srcG[e] = w * sourceGradient(cs.joint, cs.dof, cs.parent, s.js, s.sub1 + kC1 * cs.tin);
+        srcG[e] = w * sourceGradientT(cs.joint, cs.dof, cs.parent, s.js, s.sub1 + kC1 * cs.tin);
       }
     }
     __syncthreads();
@@ -2357,7 +2357,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       if (perSource) {
         for (int e = tid; e < nsrc; e += 256) {
           const int info = s.mInfo[e];
-          perS[e] = s.mW[e] * sourceGradient(info & 0xfff, (info >> 12) & 7, (info >> 16) - 1, s.js, refSub + kC1 * (s.mTin[e] & 0xffff));
+          perS[e] = s.mW[e] * sourceGradientT(info & 0xfff, (info >> 12) & 7, (info >> 16) - 1, s.js, refSub + kC1 * (s.mTin[e] & 0xffff));
         }
         __syncthreads();
       }
@@ -2369,7 +2369,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
               return perS[sl];
             }
             const int info = s.mInfo[sl];
-            return s.mW[sl] * sourceGradient(info & 0xfff, (info >> 12) & 7, (info >> 16) - 1, s.js, refSub + kC1 * (s.mTin[sl] & 0xffff));
+            return s.mW[sl] * sourceGradientT(info & 0xfff, (info >> 12) & 7, (info >> 16) - 1, s.js, refSub + kC1 * (s.mTin[sl] & 0xffff));
           };
           a = slotShare(c); // the primary slot, then the extras
           const int e1 = NP + s.mStart[c + 1];
@@ -3078,7 +3078,7 @@ __global__ void __launch_bounds__(64 * kWaves, kCompact ? 2 : 1) treeNormalEquat
       }
     }
     if (hasParamRows) {
-      e += paramRowsError<true>(rig, pb, P, s.th, b, tid);
+      e += paramRowsErrorT<true, float>(rig, pb, P, s.th, b, tid);
     }
     if (hasGen) {
       e += generalRowsEvaluate(pb, s.js, b, U, tid, x.gEv, x.gRes);
@@ -3176,7 +3176,7 @@ __global__ void __launch_bounds__(64 * kWaves, kCompact ? 2 : 1) treeNormalEquat
     o[0] = w * al.x, o[sst] = w * al.y, o[2 * sst] = w * al.z;
     o[3 * sst] = w * bv.x, o[4 * sst] = w * bv.y, o[5 * sst] = w * bv.z;
     o[6 * sst] = w * bs;
-    srcG[e] = w * sourceGradient(cs.joint, cs.dof, cs.parent, jsE, s.sub1 + kC1 * cs.tin);
+    srcG[e] = w * sourceGradientT(cs.joint, cs.dof, cs.parent, jsE, s.sub1 + kC1 * cs.tin);
   }
   __syncthreads();
   MMX_TCLK(5)
@@ -3663,7 +3663,7 @@ __global__ void __launch_bounds__(64 * kWaves, kWaves == 4 ? 2 : 1) treeRefineKe
     if (c < n) {
       auto slotShare = [&](int e) {
         const ColumnSourceDev cs = fd.srcs[e];
-        return cs.weight * sourceGradient(cs.joint, cs.dof, cs.parent, s.js, s.sub1 + kC1 * cs.tin);
+        return cs.weight * sourceGradientT(cs.joint, cs.dof, cs.parent, s.js, s.sub1 + kC1 * cs.tin);
       };
       a = slotShare(c);
       const int e1 = fd.slotBase + fd.srcStart[c + 1];

@@ -290,34 +290,6 @@ __device__ __forceinline__ ParamColD paramRowsColumnD(
   }
   return o;
 }
-// this thread's share of the parameter-space blocks' error at `th` in double (paramRowsError of mmx_device.hpp with T = double)
-template <bool kJacobianRows>
-__device__ __forceinline__ double paramRowsErrorD(const RigDev& rig, const ProblemDev& pb, int P, const double* th, int b, int tid) {
-  double e = 0.0;
-  if (pb.NL > 0 && pb.wLimit > 0.f) {
-    const double tWeight = double(1e+1f * pb.wLimit);
-    for (int l = tid; l < pb.NL; l += 256) {
-      e += evalLimit<double>(rig, pb.limits[l], th, pb.enabledMask, tWeight).err;
-    }
-  }
-  if (pb.hasModel && pb.wModel > 0.f) {
-    const float* tp = pb.mpTarget + size_t(b) * P;
-    const float* tw = pb.mpWeights + size_t(b) * P;
-    double em = 0.0;
-    for (int i = tid; i < P; i += 256) {
-      if (pb.enabledMask[i] != 0) {
-        const double w = double(tw[i]);
-        if (!kJacobianRows || w > 0.0) {
-          const double pd = w * (th[i] - double(tp[i]));
-          em += pd * pd;
-        }
-      }
-    }
-    e += em * double(pb.wModel) * 1e-1;
-  }
-  return e;
-}
-
 // y = A x for a CSR matrix whose tables live in GLOBAL memory (the wide kernels; the fused solve keeps them in LDS):
 // four rows per trip with their row bounds, then their first entries, requested together -- a row's walk is a chain
 // of dependent L2 round trips otherwise.  Same products in the same order as the plain walk.

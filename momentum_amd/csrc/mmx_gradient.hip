@@ -8,7 +8,7 @@
 //         a solve reports at these parameters)
 //   C     units: residual, sigma, error (in double); per unit the first-order moments of sigma^2 f (kC1 = 7 channels F | N | D)
 //   D     own sums per joint by DFS position, subtree sums on the matrix cores (treeSumT<kC1, true>)
-//   F     per solved column the sum of weight x sourceGradient over its sources in table order, plus the parameter-space
+//   F     per solved column the sum of weight x sourceGradientT over its sources in table order, plus the parameter-space
 //         rows (limits, model-parameter prior) evaluated on the fly from theta; x 2, scattered through the solve list
 //
 // No second-order channels, no H, no factor.  Every output entry is summed by one thread in a fixed order and no instance
@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(256) evalGradientKernel(
   }
   const bool hasParamRows = pb.M > pb.rowsJoint; // limit / model-parameter rows present (uniform)
   if (hasParamRows) {
-    e += paramRowsError<true>(rig, pb, P, s.th, b, tid);
+    e += paramRowsErrorT<true, float>(rig, pb, P, s.th, b, tid);
   }
   e = waveReduceSum(e);
   if (lane == 0) {
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(256) evalGradientKernel(
   for (int c = tid; c < n; c += kT) {
     auto slotShare = [&](int e2) {
       const ColumnSourceDev cs = fd.srcs[e2];
-      return cs.weight * sourceGradient(cs.joint, cs.dof, cs.parent, s.js, s.sub1 + kC1 * cs.tin);
+      return cs.weight * sourceGradientT(cs.joint, cs.dof, cs.parent, s.js, s.sub1 + kC1 * cs.tin);
     };
     float a = slotShare(c);
     const int e1 = fd.slotBase + fd.srcStart[c + 1];

@@ -3258,7 +3258,7 @@ __global__ void __launch_bounds__(256) stepUpdateKernel(
       }
     }
     if (pb.M > pb.rowsJoint) {
-      e += paramRowsError<false>(rig, pb, P, thT, b, tid);
+      e += paramRowsErrorT<false, float>(rig, pb, P, thT, b, tid);
     }
     e = waveReduceSum(e);
     __syncthreads();

@@ -11,25 +11,22 @@
 // cond x eps_f32 < 1.  The reference instantiates the whole path in double (momentum/solver/gauss_newton_solver.cpp:315-316,
 // SolverT<double>); this route reproduces that instantiation's answers to ~1e-7 at close to the single-precision rate.
 //
-// Formulas: tests/tree_algebra_np.py (jt_times, j_times), the double twins of mmx_tree.hpp / mmx_fused.hip phase J.
+// Formulas: tests/tree_algebra_np.py (jt_times, j_times); the templates of mmx_tree.hpp / mmx_device.hpp with T = double.
 #pragma once
 
 #include "mmx_device.hpp"
-#include "mmx_device_d.hpp"
 
 namespace mmx {
 
-constexpr int kJsD = 17; // doubles per joint: world t(3) q(4) s(1) | rotation axes x, y, z (9)  (= kJs)
 constexpr int kTanD = 8; // tangent-pass doubles per joint: C(3) W(3) S(1) | jump target (int bits)
 // damping floor of the mixed route's single-precision factor (fraction of the mean diagonal of J^T J; kFactorDamping of
 // mmx_device.hpp for the single-precision routes).  The factor is only the preconditioner here: A/B variants mixf6 / mixf7
 constexpr float kMixFactorDamping = 1e-6f;
-constexpr double kLn2D = 0.693147180559945309417232121458176568; // momentum/math/constants.h:30,40
 
 // the double arrays of one instance in LDS
 struct MixLds {
   double* th; // [P] theta
-  double* js; // [kJsD J] joint states
+  double* js; // [kJs J] joint states
   double* up; // [3 U] unit world vectors
   double* uf; // [3 U] unit residuals f (unscaled)
   double* us; // [U] sigma = sqrt(w loss')
@@ -54,7 +51,7 @@ __host__ __device__ inline size_t mixYDoubles(int J, int P) {
   return size_t(kTanD * J > P ? kTanD * J : P);
 }
 __host__ __device__ inline size_t mixPersistentDoubles(int J, int P, int U, int NP) {
-  return size_t(P) + size_t(kJsD) * J + 7 * size_t(U) + 5 * size_t(NP);
+  return size_t(P) + size_t(kJs) * J + 7 * size_t(U) + 5 * size_t(NP);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -90,9 +87,9 @@ __device__ __forceinline__ void fkLocalFromParamsD(const double* p, const float*
   mixSinCos(0.5 * p[4], &sy, &cy);
   mixSinCos(0.5 * p[5], &sz, &cz);
   const DQ q0{double(pre[0]), double(pre[1]), double(pre[2]), double(pre[3])};
-  const DQ q1 = dqmul(q0, DQ{0.0, 0.0, sz, cz});
-  const DQ q2 = dqmul(q1, DQ{0.0, sy, 0.0, cy});
-  const DQ ql = dqmul(q2, DQ{sx, 0.0, 0.0, cx});
+  const DQ q1 = qmul(q0, DQ{0.0, 0.0, sz, cz});
+  const DQ q2 = qmul(q1, DQ{0.0, sy, 0.0, cy});
+  const DQ ql = qmul(q2, DQ{sx, 0.0, 0.0, cx});
   o[0] = double(off[0]) + p[0], o[1] = double(off[1]) + p[1], o[2] = double(off[2]) + p[2];
   o[3] = ql.x, o[4] = ql.y, o[5] = ql.z, o[6] = ql.w;
   o[7] = exp2(p[6]);
@@ -109,28 +106,21 @@ __device__ __forceinline__ void fkStoreLocalDD(double* bufA, int Jp, int j, cons
 __device__ __forceinline__ void fkAxesInPlaceD(const float* pre, int j, int par, double* js) {
   DQ qp{0.0, 0.0, 0.0, 1.0};
   if (par >= 0) {
-    const double* p = js + kJsD * par;
+    const double* p = js + kJs * par;
     qp = DQ{p[3], p[4], p[5], p[6]};
   }
-  double* o = js + kJsD * j;
-  const D3 az = dqrot(dqmul(qp, DQ{double(pre[0]), double(pre[1]), double(pre[2]), double(pre[3])}), D3{0.0, 0.0, 1.0});
-  const D3 ay = dqrot(dqmul(qp, DQ{o[8], o[9], o[10], o[11]}), D3{0.0, 1.0, 0.0});
-  const D3 ax = dqrot(dqmul(qp, DQ{o[12], o[13], o[14], o[15]}), D3{1.0, 0.0, 0.0});
+  double* o = js + kJs * j;
+  const D3 az = qrot(qmul(qp, DQ{double(pre[0]), double(pre[1]), double(pre[2]), double(pre[3])}), D3{0.0, 0.0, 1.0});
+  const D3 ay = qrot(qmul(qp, DQ{o[8], o[9], o[10], o[11]}), D3{0.0, 1.0, 0.0});
+  const D3 ax = qrot(qmul(qp, DQ{o[12], o[13], o[14], o[15]}), D3{1.0, 0.0, 0.0});
   o[8] = ax.x, o[9] = ax.y, o[10] = ax.z;
   o[11] = ay.x, o[12] = ay.y, o[13] = ay.z;
   o[14] = az.x, o[15] = az.y, o[16] = az.z;
 }
-// translationAxis column d of a joint = column d of parent.toLinear() (joint_state.cpp:36-42)
-__device__ __forceinline__ D3 transAxisColD(const double* js, int parent, int d) {
-  if (parent < 0) {
-    return D3{d == 0 ? 1.0 : 0.0, d == 1 ? 1.0 : 0.0, d == 2 ? 1.0 : 0.0};
-  }
-  const double* p = js + kJsD * parent;
-  return p[7] * dqmatCol(DQ{p[3], p[4], p[5], p[6]}, d);
-}
-
 // Position / Orientation evalFunction + the weighting of JointErrorFunctionT<double>::getJacobian
-// (position_error_function.cpp:15-27, orientation_error_function.cpp:15-40, joint_error_function-inl.h:197-213)
+// (position_error_function.cpp:15-27, orientation_error_function.cpp:15-40, joint_error_function-inl.h:197-213).
+// Not one template with evalUnitFrom (mmx_device.hpp): that one picks its loss record by reference, this one by value (below),
+// and either form in the other's place changes the other's kernel.
 struct UnitD {
   D3 v, f;
   double sigma, werr;
@@ -142,7 +132,7 @@ __device__ __forceinline__ UnitD evalUnitD(const ProblemDev& pb, const UnitInput
   if (u >= pb.U) {
     return o;
   }
-  const double* w = js + kJsD * in.joint;
+  const double* w = js + kJs * in.joint;
   const D3 t{w[0], w[1], w[2]};
   const DQ q{w[3], w[4], w[5], w[6]};
   const bool isPoint = u < pb.Kp;
@@ -155,24 +145,24 @@ __device__ __forceinline__ UnitD evalUnitD(const ProblemDev& pb, const UnitInput
   const float fwP = pb.wPos, fwO = pb.wOri;
   const LossDev ls{isPoint ? lsP.type : lsO.type, isPoint ? lsP.alpha : lsO.alpha, isPoint ? lsP.invC2 : lsO.invC2, isPoint ? lsP.c : lsO.c};
   if (isPoint) {
-    o.v = t + dqrot(q, w[7] * D3{double(in.a[0]), double(in.a[1]), double(in.a[2])});
+    o.v = t + qrot(q, w[7] * D3{double(in.a[0]), double(in.a[1]), double(in.a[2])});
     o.f = o.v - D3{double(in.t[0]), double(in.t[1]), double(in.t[2])};
-    sqr = ddot(o.f, o.f);
+    sqr = dot(o.f, o.f);
     fw = double(fwP);
   } else {
     const int uo = u - pb.Kp, k = uo - 3 * (uo / 3);
     // OrientationDataT<double>'s constructor normalises in double (orientation_error_function.h:33-35)
-    const DQ qo = dqnormalized(DQ{double(in.a[0]), double(in.a[1]), double(in.a[2]), double(in.a[3])});
-    const DQ qt = dqnormalized(DQ{double(in.t[0]), double(in.t[1]), double(in.t[2]), double(in.t[3])});
-    o.v = dqrot(q, dqmatCol(qo, k));
-    o.f = o.v - dqmatCol(qt, k);
-    sqr = ddot(o.f, o.f);
+    const DQ qo = qnormalized(DQ{double(in.a[0]), double(in.a[1]), double(in.a[2]), double(in.a[3])});
+    const DQ qt = qnormalized(DQ{double(in.t[0]), double(in.t[1]), double(in.t[2]), double(in.t[3])});
+    o.v = qrot(q, qmatCol(qo, k));
+    o.f = o.v - qmatCol(qt, k);
+    sqr = dot(o.f, o.f);
     if (ls.type != 0) { // a robust loss sees all nine rows of the constraint
       first = k == 0;
       for (int kk = 0; kk < 3; ++kk) {
         if (kk != k) {
-          const D3 fo = dqrot(q, dqmatCol(qo, kk)) - dqmatCol(qt, kk);
-          sqr += ddot(fo, fo);
+          const D3 fo = qrot(q, qmatCol(qo, kk)) - qmatCol(qt, kk);
+          sqr += dot(fo, fo);
         }
       }
     }
@@ -185,27 +175,11 @@ __device__ __forceinline__ UnitD evalUnitD(const ProblemDev& pb, const UnitInput
       o.werr = wgt * (sqr * ic);
       o.sigma = sqrt(wgt * ic);
     } else {
-      o.werr = first ? wgt * dlossValue(ls, sqr) : 0.0;
-      o.sigma = sqrt(wgt * dlossDeriv(ls, sqr));
+      o.werr = first ? wgt * lossValue(ls, sqr) : 0.0;
+      o.sigma = sqrt(wgt * lossDeriv(ls, sqr));
     }
   }
   return o;
-}
-
-// J^T y component of one (joint, dof) from the first-order subtree sums F(3) N(3) D (mmx_tree.hpp sourceGradient in double)
-__device__ __forceinline__ double sourceGradientD(int joint, int dof, int parent, const double* js, const double* sb) {
-  const double* a = js + kJsD * joint;
-  const D3 ta{a[0], a[1], a[2]};
-  const D3 Fv{sb[0], sb[1], sb[2]};
-  if (dof < 3) {
-    return ddot(transAxisColD(js, parent, dof), Fv);
-  }
-  if (dof < 6) {
-    const double* ax = a + 8 + 3 * (dof - 3);
-    const D3 Nv{sb[3], sb[4], sb[5]};
-    return ddot(D3{ax[0], ax[1], ax[2]}, Nv - dcross(ta, Fv));
-  }
-  return kLn2D * (sb[6] - ddot(ta, Fv));
 }
 
 __device__ __forceinline__ double blockSumD(double* red, double v, int tid) {

@@ -6,16 +6,6 @@
 
 namespace mmx {
 
-// translationAxis column d of joint a = column d of parent.toLinear() (joint_state.cpp:36-42)
-__device__ __forceinline__ F3 transAxisCol(const float* js, int parent, int d) {
-  if (parent < 0) {
-    return F3{d == 0 ? 1.f : 0.f, d == 1 ? 1.f : 0.f, d == 2 ? 1.f : 0.f};
-  }
-  const float* p = js + kJs * parent;
-  const F3 c = qmatCol(Q4{p[3], p[4], p[5], p[6]}, d);
-  return F3{c.x * p[7], c.y * p[7], c.z * p[7]};
-}
-
 constexpr int kC2 = 17; // second-order channels per joint: m0 | m1(3) | M2 (xx xy xz yy yz zz) | M2 of directions (6) | pad (odd stride)
 constexpr int kC2Used = 16;
 constexpr int kC1 = 7; // first-order channels per joint: F(3) | N(3) | D (odd stride)
@@ -118,20 +108,21 @@ __device__ __forceinline__ void treeSumRanges(const I* subSize, const I* loadedP
   }
 }
 
-// J^T y component of one (joint, dof) from the first-order subtree sums (tests/tree_algebra_np.py jt_times)
-__device__ __forceinline__ float sourceGradient(int joint, int dof, int parent, const float* js, const float* sb) {
-  const float* a = js + kJs * joint;
-  const F3 ta{a[0], a[1], a[2]};
-  const F3 Fv{sb[0], sb[1], sb[2]};
+// J^T y component of one (joint, dof) from the first-order subtree sums F(3) N(3) D (tests/tree_algebra_np.py jt_times)
+template <class T>
+__device__ __forceinline__ T sourceGradientT(int joint, int dof, int parent, const T* js, const T* sb) {
+  const T* a = js + kJs * joint;
+  const Vec3T<T> ta{a[0], a[1], a[2]};
+  const Vec3T<T> Fv{sb[0], sb[1], sb[2]};
   if (dof < 3) {
     return dot(transAxisCol(js, parent, dof), Fv);
   }
   if (dof < 6) {
-    const float* ax = a + 8 + 3 * (dof - 3);
-    const F3 Nv{sb[3], sb[4], sb[5]};
-    return dot(F3{ax[0], ax[1], ax[2]}, Nv - cross(ta, Fv));
+    const T* ax = a + 8 + 3 * (dof - 3);
+    const Vec3T<T> Nv{sb[3], sb[4], sb[5]};
+    return dot(Vec3T<T>{ax[0], ax[1], ax[2]}, Nv - cross(ta, Fv));
   }
-  return kLn2 * (sb[6] - dot(ta, Fv));
+  return kLn2T<T> * (sb[6] - dot(ta, Fv));
 }
 
 } // namespace mmx
