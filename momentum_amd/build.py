@@ -82,7 +82,7 @@ def build_info() -> dict:
         return {}
 # sources that include another source: their objects are rebuilt when that one changes
 SOURCE_DEPS = {"mmx_wave_frames.hip": ["mmx_wave.hip"]}
-HEADERS = ["mmx_device.hpp", "mmx_kernels.hpp", "mmx_tree.hpp", "mmx_fused_helpers.hpp", "mmx_host_tables.hpp", "mmx_solve_plan.hpp", "mmx_constraint_intake.hpp", os.path.join("..", "..", "include", "mmx.h")]
+HEADERS = ["mmx_device.hpp", "mmx_kernels.hpp", "mmx_tree.hpp", "mmx_fused_helpers.hpp", "mmx_mixed.hpp", "mmx_solver_rules.hpp", "mmx_host_tables.hpp", "mmx_solve_plan.hpp", "mmx_constraint_intake.hpp", os.path.join("..", "..", "include", "mmx.h")]
 ARCH = "gfx950"
 
 

@@ -19,6 +19,7 @@
 
 #include "../../include/mmx.h"
 #include "mmx_constraint_intake.hpp"
+#include "mmx_solver_rules.hpp"
 
 namespace mmx {
 

@@ -1577,7 +1577,7 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
       __syncthreads();
       double lam = 1e-10;
       bool haveStep = false; // s.d solves the system of the current damping
-      for (int trustStep = 0; trustStep < 10; ++trustStep) { // :157
+      for (int trustStep = 0; trustStep < kTrustMaxTrials; ++trustStep) {
         double mu = 0.0, dn2 = 0.0, dg = 0.0;
         bool noStep = false;
         int pdRetries = 0;
@@ -1621,11 +1621,11 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
           }
           dn2 = blockSumF64(s, p0, tid);
           dg = blockSumF64(s, p1, tid);
-          if (newton == 0 && 2.0 * dg < double(FLT_EPSILON) * (1.0 + curError)) { // :164 (gradientSub_ = 2 J^T r): not worth a step
+          if (trustGradientTooSmall(newton, dg, curError)) {
             noStep = true;
             break;
           }
-          if (newton < 3 && sqrt(dn2) >= 1.05 * trRadius) { // :180-181
+          if (newton < 3 && sqrt(dn2) >= 1.05 * trRadius) { // (trustWantsNewton, mmx_solver_rules.hpp, spelled out only to keep this kernel's register allocation the one it had: with the call it spills 118 scalar registers instead of 120)
             // Newton step on lambda (Nocedal & Wright eq. 4.44, :191-204): p_l = -(step), |q_l|^2 = p_l^T (R^T R)^-1 p_l
             solveLLt(s.d, s.trial);
             double pq = 0.0;
@@ -1633,10 +1633,9 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
               pq += s.d[c] * s.trial[c];
             }
             const double q2 = blockSumF64(s, pq, tid);
-            if (q2 >= double(FLT_EPSILON)) { // :198
-              const double pn = sqrt(dn2);
-              const double deltaLambda = (dn2 / q2) * ((pn - trRadius) / trRadius);
-              if (deltaLambda > 0.0) { // :207: lambda only ever grows
+            if (trustNewtonDefined(q2)) {
+              const double deltaLambda = trustDeltaLambda(dn2, q2, trRadius);
+              if (deltaLambda > 0.0) { // lambda only ever grows
                 lam += deltaLambda;
                 ++newton;
                 haveStep = false;
@@ -1653,20 +1652,16 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
         // p^T J^T J p = g.p - mu |p|^2 because (J^T J + mu I) p = g  (:240-247)
         makeTrial(1.0);
         const double eNew = errorF64(rig, pb, s, s.trial, b, tid);
-        const double predicted = dg + (mu - 1e-20) * dn2; // e - model
-        const double rho = (curError - eNew) / predicted;
-        if (rho < 0.25) { // :256-262
-          trRadius = 0.25 * trRadius;
-        } else if (rho > 0.75 && lam > 0.0) {
-          trRadius = fmin(2.0 * trRadius, 10.0);
-        }
+        const double predicted = trustPredicted(dg, mu, dn2);
+        const double rho = gainRatio(curError, eNew, predicted);
+        trRadius = trustNextRadius(rho, trRadius, lam > 0.0);
         if (rho > 0.0) { // :265
           acceptTrial();
           break;
         }
       }
       notPd = false; // (the rule's own retries dealt with it)
-    } else if (!notPd && fp.stepRule == 1) {
+    } else if (!notPd && fp.stepRule == MMX_STEP_LM_SCHEDULE) {
       double part = 0.0;
       for (int c = tid; c < n; c += 256) {
         part += s.d[c] * s.g[c] + lambda * s.d[c] * s.d[c];
@@ -1674,7 +1669,7 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
       const double predicted = blockSumF64(s, part, tid);
       makeTrial(1.0);
       const double eNew = errorF64(rig, pb, s, s.trial, b, tid);
-      const double rho = predicted > 0.0 ? (curError - eNew) / predicted : -1.0;
+      const double rho = lmGainRatio(curError, eNew, predicted);
       if (st.stepHistory != nullptr && tid == 0) {
         double* sh = st.stepHistory + (size_t(b) * fp.maxIterations + it) * 2;
         sh[0] = lambda;
@@ -1683,19 +1678,15 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
       if (rho > 0.0) {
         acceptTrial();
       }
-      if (!(rho >= 0.25)) {
-        lambda = fmin(lambda * double(fp.lmUp), double(fp.lmLambdaMax));
-      } else if (rho > 0.75) {
-        lambda = fmax(lambda * double(fp.lmDown), double(fp.lmLambdaMin));
-      }
-    } else if (notPd && fp.stepRule == 1) {
+      lambda = lmNextLambda(lambda, rho, double(fp.lmUp), double(fp.lmDown), double(fp.lmLambdaMin), double(fp.lmLambdaMax));
+    } else if (notPd && fp.stepRule == MMX_STEP_LM_SCHEDULE) {
       if (st.stepHistory != nullptr && tid == 0) {
         double* sh = st.stepHistory + (size_t(b) * fp.maxIterations + it) * 2;
         sh[0] = lambda;
         sh[1] = -1.0;
       }
-      lambda = fmin(lambda * double(fp.lmUp), double(fp.lmLambdaMax));
-    } else if (!notPd && fp.doLineSearch == 2) {
+      lambda = lmRaisedLambda(lambda, double(fp.lmUp), double(fp.lmLambdaMax));
+    } else if (!notPd && fp.doLineSearch == MMX_LINE_SEARCH_DIRECTIONAL) {
       double part = 0.0;
       for (int c = tid; c < n; c += 256) {
         part += s.g[c] * s.d[c];
@@ -1705,19 +1696,19 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
       for (int ls = 0; ls < 10; ++ls) {
         makeTrial(double(alpha));
         const double eNew = errorF64(rig, pb, s, s.trial, b, tid);
-        if ((curError - eNew) >= double(1e-4f * alpha) * gd) {
+        if (armijoAccepts(MMX_LINE_SEARCH_DIRECTIONAL, curError, eNew, alpha, 0.0, gd)) {
           break;
         }
         alpha *= 0.5f;
       }
       acceptTrial();
-    } else if (!notPd && fp.doLineSearch == 1) {
+    } else if (!notPd && fp.doLineSearch == MMX_LINE_SEARCH_GAUSS_NEWTON) {
       const double scaledError = 1e-3 * curError;
       double scale = 1.0;
       for (int ls = 0; ls < 10; ++ls) {
         makeTrial(scale);
         const double eNew = errorF64(rig, pb, s, s.trial, b, tid);
-        if ((curError - eNew) >= scale * scaledError) {
+        if (armijoAccepts(MMX_LINE_SEARCH_GAUSS_NEWTON, curError, eNew, scale, scaledError, 0.0)) {
           break;
         }
         scale *= 0.5;
@@ -1734,10 +1725,9 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
       }
       itersDone = it + 1;
       if (notPd) {
-        s.flags[2] = 2;
+        s.flags[2] = MMX_SOLVE_NOT_PD;
       }
-      const bool converged = fabs(lastError - curError) / (fabs(curError) + double(FLT_MIN)) <= double(fp.threshold) * double(FLT_EPSILON);
-      s.flags[0] = (it >= fp.minIterations && converged) ? 1 : 0;
+      s.flags[0] = solveStops(it, fp.minIterations, lastError, curError, fp.threshold) ? 1 : 0;
       lastError = curError;
     }
     __syncthreads();
@@ -1787,8 +1777,8 @@ __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
   if (tid == 0) {
     st.iterations[b] = itersDone;
     st.finalError[b] = curError;
-    // (escalated: the double run's status + why the element was taken + MMX_SOLVE_ESCALATED_F64)
-    st.status[b] = (bad ? 1 : s.flags[2]) | (sel.map != nullptr ? ((st.status[b] & 8) | 16) : 0);
+    const int32_t own = solveStatus(bad, s.flags[2]);
+    st.status[b] = sel.map != nullptr ? escalatedStatus(own, st.status[b]) : own;
   }
 }
 

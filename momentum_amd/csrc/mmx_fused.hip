@@ -1380,8 +1380,8 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
   // schedule, blockError<kStore>); stateError = the error an evaluation of phases A-C would report for it
   // (measured: line search 1.39 -> 1.52e6, LM schedule 1.41 -> 1.53e6 solves/s at cfg2 / cfg3)
   constexpr bool kReuse = !kGen && !kTR && kRule != 0;
-  const int stepRule = kRule < 0 ? fp.stepRule : (kRule == 1 ? 1 : 0);
-  const int doLineSearch = kRule < 0 || kRule == 2 ? fp.doLineSearch : 0;
+  const int stepRule = kRule < 0 ? fp.stepRule : (kRule == 1 ? MMX_STEP_LM_SCHEDULE : MMX_STEP_GN_FIXED_LAMBDA);
+  const int doLineSearch = kRule < 0 || kRule == 2 ? fp.doLineSearch : MMX_LINE_SEARCH_NONE;
   bool stateValid = false;
   double stateError = 0.0;
   // (the parameter transform's CSR in global memory is walked twice per iteration by the instantiations without an LDS copy.  Two
@@ -1414,8 +1414,8 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     int trustStep = 0;
     bool trNoStep = false; // the step is not worth taking (:164) or could not be computed: the parameters stay
     float trDn2 = 0.f, trDg = 0.f, trMu = 0.f; // |step|^2, step . J^T r, damping of the step on the table
-    bool notPd = false; // (kept false since the pivot floor: the factorisation always completes and the step is always taken, as in
-                        // the reference, which never looks at LLT::info(); the branches it guards are dead code the compiler removes)
+    // (since the pivot floor the factorisation always completes and the step is always taken, as in the reference, which never
+    // looks at LLT::info())
     bool badPivot = false; // a raw pivot was not positive: reported as MMX_SOLVE_NOT_PD
     bool floored = false; // the factor's damping floor exceeded the caller's damping: reported as MMX_SOLVE_DAMPING_FLOORED
     for (;;) {
@@ -1496,7 +1496,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       __syncthreads();
       MMX_CLK(5)
     }
-    int newtonIter = 0, pdRetries = 0;
+    int newtonIter = 0;
     for (;;) { // one pass per value of the damping (the trust region's Newton updates change it, :180-231)
     int tidS = tid;
     if (kTR) {
@@ -2181,7 +2181,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       mixUnconverged = mixUnconverged || !converged;
     } else if (kRide) { // (blocks 0 .. NB - 2 of the forward substitution were solved under the panels: the last block and the backward sweep)
       solveLLtAheadTail<NB>(s.L, s.invDiag, s.d0, tid);
-    } else if (!notPd) {
+    } else {
       solveLLt<NB, kLeanSolve>(s.L, s.invDiag, s.d0, tid);
     }
     MMX_CLK(8)
@@ -2194,7 +2194,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     // (refinement steps allowed: default 3, mmx_tuning::max_refinement_steps.  Round 6 measured leaving the refinement out of the
     // FIRST three / five iterations only -- + 5.6 % / + 10 % -- and every instance left the bound, median 3.4e-5: ten damped
     // iterations do not attenuate an early step's error at all; profiles/r06_exp_fused.txt)
-    const int nRefine = (!notPd && !kMix) ? fp.refine : 0;
+    const int nRefine = !kMix ? fp.refine : 0;
     float prevCorr2 = FLT_MAX;
     for (int rf = 0; rf < nRefine; ++rf) {
       // joint-parameter delta jd = transform * delta (delta gathered through the solve map)
@@ -2411,9 +2411,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       const float step2 = float((s.red[0] + s.red[1]) + (s.red[2] + s.red[3]));
       refineWorst = fmaxf(refineWorst, corr2 * __builtin_amdgcn_rcpf(fmaxf(step2, 1e-37f))); // (mmx_problem_solve_diagnostics; uniform)
       __syncthreads();
-      // a correction is only taken when it is a contraction (kRefineMax2, mmx_kernels.hip: where the fp32 factor is no
-      // preconditioner any more -- pivots at rounding level -- the refinement diverges): undo it and stop
-      if (corr2 > 0.25f * step2 || corr2 > prevCorr2) {
+      if (refineUndo(corr2, step2, prevCorr2)) { // not a contraction
         for (int c = tid; c < n; c += 256) {
           s.d0[c] -= s.rho[c];
         }
@@ -2421,7 +2419,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
         break;
       }
       prevCorr2 = corr2;
-      if (!(corr2 > 1e-6f * step2)) {
+      if (!refineAgain(corr2, step2)) {
         break;
       }
     }
@@ -2430,14 +2428,6 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       break;
     }
     // ---- trust region: is this step the one to try, or does the damping have to grow first?
-    if (notPd) { // (cannot happen in the reference's QR) more damping, a bounded number of times
-      trLambda = fmaxf(4.f * trLambda, 1e-6f);
-      if (++pdRetries > 16) {
-        trNoStep = true;
-        break;
-      }
-      continue;
-    }
     {
       float p0 = 0.f, p1 = 0.f;
       for (int c = tid; c < n; c += 256) {
@@ -2448,11 +2438,11 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       trDg = blockSumF(s, p1, tid);
       trMu = mu;
     }
-    if (newtonIter == 0 && 2.f * trDg < FLT_EPSILON * (1.f + float(curError))) { // :164 (gradientSub_ = 2 J^T r)
+    if (trustGradientTooSmall(newtonIter, trDg, curError)) {
       trNoStep = true;
       break;
     }
-    if (newtonIter < 3 && sqrtf(trDn2) >= 1.05f * trRadius) { // :180-181
+    if (trustWantsNewton(newtonIter, trDn2, trRadius)) {
       // Newton step on lambda (Nocedal & Wright eq. 4.44, :191-204): p_l = -(step), |q_l|^2 = p_l^T (R^T R)^-1 p_l
       for (int c = tid; c < NP; c += 256) {
         s.rho[c] = c < n ? s.d0[c] : 0.f;
@@ -2464,10 +2454,9 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
         pq += s.d0[c] * s.rho[c];
       }
       const float q2 = blockSumF(s, pq, tid);
-      if (q2 >= FLT_EPSILON) { // :198
-        const float pn = sqrtf(trDn2);
-        const float deltaLambda = (trDn2 / q2) * ((pn - trRadius) / trRadius);
-        if (deltaLambda > 0.f) { // :207: lambda only ever grows
+      if (trustNewtonDefined(q2)) {
+        const float deltaLambda = trustDeltaLambda(trDn2, q2, trRadius);
+        if (deltaLambda > 0.f) { // lambda only ever grows
           trLambda += deltaLambda;
           ++newtonIter;
           continue; // factor and solve again with the larger damping (the reference appends rows to its QR)
@@ -2481,7 +2470,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     if (kMix) {
       // ---- the step rules of phase K as the DOUBLE instantiation takes them (oracle: solveGaussNewton<double>): theta, the
       // trial parameters (m.Y) and the errors in double; the LM schedule's damping in double, its rounding is what is factored
-      if (stepRule == 1) {
+      if (stepRule == MMX_STEP_LM_SCHEDULE) {
         double part = 0.0;
         for (int c = tid; c < n; c += 256) {
           part += m.x[c] * m.g[c] + lambdaD * m.x[c] * m.x[c];
@@ -2497,7 +2486,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
         __syncthreads();
         double eFull = 0.0;
         const double eNew = blockErrorD<true>(rv, pb, s, m, m.Y, b, U, tid, mixLevel, &eFull, mixRecP, &rig, hasParamRows);
-        const double rho = predicted > 0.0 ? (curError - eNew) / predicted : -1.0;
+        const double rho = lmGainRatio(curError, eNew, predicted);
         if (st.stepHistory != nullptr && tid == 0) {
           double* sh = st.stepHistory + (size_t(b) * fp.maxIterations + it) * 2;
           sh[0] = lambdaD;
@@ -2511,16 +2500,12 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
           stateValid = !hasParamRows; // (the trial's error is getError's: with parameter-space rows the iteration's is getJacobian's)
           stateError = eFull;
         }
-        if (!(rho >= 0.25)) {
-          lambdaD = fmin(lambdaD * double(fp.lmUp), double(fp.lmLambdaMax));
-        } else if (rho > 0.75) {
-          lambdaD = fmax(lambdaD * double(fp.lmDown), double(fp.lmLambdaMin));
-        }
+        lambdaD = lmNextLambda(lambdaD, rho, double(fp.lmUp), double(fp.lmDown), double(fp.lmLambdaMin), double(fp.lmLambdaMax));
         lambda = float(lambdaD);
       } else if (doLineSearch) { // both backtracking rules (gauss_newton_solver.cpp:283-313, subset_gauss_newton_solver.cpp:117-142)
         const double scaledError = 1e-3 * curError;
         double gd = 0.0;
-        if (doLineSearch == 2) {
+        if (doLineSearch == MMX_LINE_SEARCH_DIRECTIONAL) {
           double part = 0.0;
           for (int c = tid; c < n; c += 256) {
             part += m.g[c] * m.x[c];
@@ -2538,7 +2523,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
           }
           __syncthreads();
           const double eNew = blockErrorD<true>(rv, pb, s, m, m.Y, b, U, tid, mixLevel, &stateError, mixRecP, &rig, hasParamRows);
-          if ((curError - eNew) >= (doLineSearch == 2 ? double(1e-4f * scale) * gd : double(scale) * scaledError)) {
+          if (armijoAccepts(doLineSearch, curError, eNew, scale, scaledError, gd)) {
             break;
           }
           scale *= 0.5f;
@@ -2570,26 +2555,22 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       }
       __syncthreads();
       const double eNew = blockError<kGen, false, !kCsrLds>(rig, rv, pb, fv, s, s.dfull, b, tid);
-      const float predicted = trDg + (trMu - 1e-20f) * trDn2; // e - model
-      const float rho = float((curError - eNew) / double(predicted));
-      if (rho < 0.25f) { // :256-262 (lambda > 0 always holds: it starts at 1e-10)
-        trRadius = 0.25f * trRadius;
-      } else if (rho > 0.75f) {
-        trRadius = fminf(2.f * trRadius, 10.f);
-      }
+      const float predicted = trustPredicted(trDg, trMu, trDn2);
+      const float rho = gainRatio(curError, eNew, predicted);
+      trRadius = trustNextRadius(rho, trRadius, true); // (lambda > 0 always holds: it starts at 1e-10)
       if (rho > 0.f) { // :265
         for (int i = tid; i < P; i += 256) {
           s.th[i] = s.dfull[i];
         }
         break;
       }
-      if (++trustStep >= 10) { // :157: every trial rejected, the parameters stay (:268-269)
+      if (++trustStep >= kTrustMaxTrials) {
         break;
       }
       __syncthreads();
       continue; // the trial evaluation overwrote the joint states and the factor: this theta once more
     }
-    if (!notPd && stepRule == 1) {
+    if (stepRule == MMX_STEP_LM_SCHEDULE) {
       // ---- LM gain-ratio schedule, the lambda form of TrustRegionQRT's radius rule
       // (momentum/character_solver/trust_region_qr.cpp:244-268); identical to the oracle's
       // restatement (oracle/mmx_oracle.hpp solveGaussNewton, stepRule 1)
@@ -2608,7 +2589,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       __syncthreads();
       double eFull = 0.0;
       const double eNew = blockError<kGen, kReuse, !kCsrLds>(rig, rv, pb, fv, s, s.dfull, b, tid, &eFull);
-      const float rho = predicted > 0.f ? float((curError - eNew) / double(predicted)) : -1.f;
+      const float rho = lmGainRatio(curError, eNew, predicted);
       if (st.stepHistory != nullptr && tid == 0) {
         double* sh = st.stepHistory + (size_t(b) * fp.maxIterations + it) * 2;
         sh[0] = double(lambda);
@@ -2622,26 +2603,15 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
         stateValid = kReuse && !hasParamRows;
         stateError = eFull;
       }
-      if (!(rho >= 0.25f)) {
-        lambda = fminf(lambda * fp.lmUp, fp.lmLambdaMax);
-      } else if (rho > 0.75f) {
-        lambda = fmaxf(lambda * fp.lmDown, fp.lmLambdaMin);
-      }
-    } else if (notPd && stepRule == 1) {
-      if (st.stepHistory != nullptr && tid == 0) {
-        double* sh = st.stepHistory + (size_t(b) * fp.maxIterations + it) * 2;
-        sh[0] = double(lambda);
-        sh[1] = -1.0; // no step was taken: the schedule treats it as a rejected one
-      }
-      lambda = fminf(lambda * fp.lmUp, fp.lmLambdaMax);
-    } else if (!notPd && doLineSearch) {
+      lambda = lmNextLambda(lambda, rho, fp.lmUp, fp.lmDown, fp.lmLambdaMin, fp.lmLambdaMax);
+    } else if (doLineSearch) {
       // ---- GaussNewtonSolverT::updateParameters with doLineSearch (gauss_newton_solver.cpp:283-313):
       // Armijo backtracking, c1 = 1e-3, tau = 0.5, at most 10 trial steps; the last trial stays
       // or SubsetGaussNewtonSolverT / GaussNewtonSolverQRT (subset_gauss_newton_solver.cpp:117-142,
       // gauss_newton_solver_qr.cpp:126-149): c_1 = 1e-4 against the directional derivative J^T r . delta
       const float scaledError = 1e-3f * float(curError);
       double gd = 0.0;
-      if (doLineSearch == 2) {
+      if (doLineSearch == MMX_LINE_SEARCH_DIRECTIONAL) {
         float part = 0.f;
         for (int c = tid; c < n; c += 256) {
           part += s.g[c] * s.d0[c];
@@ -2659,7 +2629,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
         }
         __syncthreads();
         const double eNew = blockError<kGen, kReuse, !kCsrLds>(rig, rv, pb, fv, s, s.dfull, b, tid, &stateError);
-        if ((curError - eNew) >= (doLineSearch == 2 ? double(1e-4f * scale) * gd : double(scale * scaledError))) {
+        if (armijoAccepts(doLineSearch, curError, eNew, scale, scaledError, gd)) {
           break;
         }
         scale *= 0.5f;
@@ -2668,7 +2638,7 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
         s.th[i] = s.dfull[i];
       }
       stateValid = kReuse && !hasParamRows; // the last trial evaluated IS the new theta
-    } else if (!notPd) {
+    } else {
       for (int c = tid; c < n; c += 256) {
         s.th[fv.solveList[c]] -= s.d0[c]; // skeleton_solver_function.cpp:158
       }
@@ -2717,20 +2687,20 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
       }
       itersDone = it + 1;
       if (badPivot && !kMix) { // (kMix: the factor is the preconditioner -- a floored pivot costs CG steps, and those are what is reported)
-        s.flags[2] |= 2; // MMX_SOLVE_NOT_PD
+        s.flags[2] |= MMX_SOLVE_NOT_PD;
       }
       if (floored) {
-        s.flags[2] |= 4; // MMX_SOLVE_DAMPING_FLOORED
+        s.flags[2] |= MMX_SOLVE_DAMPING_FLOORED;
       }
-
+      // (solveStops and, in the epilogue, precisionSuspect of mmx_solver_rules.hpp, spelled out: with the calls the generic-rule
+      // instantiation waits for a scalar load it used to overlap with the division and measured 0.2-0.7 % slower on the lines it serves)
       const bool converged = fabs(lastError - e) / (fabs(e) + double(FLT_MIN)) <= double(fp.threshold) * double(FLT_EPSILON);
       s.flags[0] = (it >= fp.minIterations && converged) ? 1 : 0;
       lastError = e;
       if (!kMix && !kTR && fp.autoAbort != 0 && st.precisionBound > 0.f) {
         // MMX_PRECISION_AUTO with a mixed-precision second pass: an element whose estimate SO FAR exceeds the bound will be solved
         // again from its initial parameters anyway -- it stops here, its parameters are not written back
-        const float estNow = kPrecisionGain * FLT_EPSILON * estAcc[1] / kPivotFloorOrOne;
-        if (!(estNow <= st.precisionBound)) {
+        if (precisionSuspect(precisionEstimate(kPrecisionGain, estAcc[1], kPivotFloorOrOne), st.precisionBound)) {
           s.flags[0] = 2; // marked: leave
         }
       }
@@ -2769,15 +2739,15 @@ __global__ void __launch_bounds__(256, (NB <= 6 && !kGen ? (FusedFour<NB, kTR, k
     // smallest pivot ratio of the whole solve.
     const float worst = estAcc[0], wS = estAcc[1];
     const float ratio = worst > 0.f ? kPivotFloorOrOne / worst : 1.f;
-    const float est = wS > 0.f ? kPrecisionGain * FLT_EPSILON * wS / kPivotFloorOrOne : kPrecisionGain * FLT_EPSILON;
-    int stt = bad ? 1 : s.flags[2];
+    const float est = wS > 0.f ? precisionEstimate(kPrecisionGain, wS, kPivotFloorOrOne) : kPrecisionGain * FLT_EPSILON;
+    int stt = bad ? MMX_SOLVE_NONFINITE : s.flags[2]; // (solveStatus, mmx_solver_rules.hpp, spelled out only to keep the mixed instantiation's register allocation the one it had: with the call it spills 282 scalar registers instead of 284)
     if (kMix) { // the estimate is the single-precision solves' (informational here): marked only when the CG did not converge
       if (!bad && mixUnconverged) {
-        stt |= 8;
+        stt |= MMX_SOLVE_PRECISION_SUSPECT;
       }
-      stt |= 32; // MMX_SOLVE_MIXED
-    } else if (!bad && st.precisionBound > 0.f && !(est <= st.precisionBound)) {
-      stt |= 8; // MMX_SOLVE_PRECISION_SUSPECT
+      stt |= MMX_SOLVE_MIXED;
+    } else if (!bad && st.precisionBound > 0.f && !(est <= st.precisionBound)) { // (precisionSuspect, spelled out: see solveStops above)
+      stt |= MMX_SOLVE_PRECISION_SUSPECT;
     }
     if (st.diag != nullptr) {
       float* dg = st.diag + 4 * size_t(b);
@@ -3797,7 +3767,7 @@ static hipError_t launchFusedNB(
     void* argsBuf,
     hipStream_t stream) {
   if (fd.GT > 0) { // further joint error functions / ellipsoid limits: the production and the parity-dump instantiations only
-    if (fp.stepRule == 2) {
+    if (fp.stepRule == MMX_STEP_TRUST_REGION) {
       return hipErrorInvalidValue;
     }
     if (dbgH != nullptr || dbgG != nullptr) {
@@ -3805,7 +3775,7 @@ static hipError_t launchFusedNB(
     }
     return launchFusedMode<NB, 0, false, true>(rig, pb, fd, theta, st, fp, nullptr, nullptr, nullptr, argsBuf, stream);
   }
-  if (fp.stepRule == 2) { // MMX_STEP_TRUST_REGION: its own instantiation (no clocks / parity dump in it)
+  if (fp.stepRule == MMX_STEP_TRUST_REGION) { // its own instantiation (no clocks / parity dump in it)
     return launchFusedMode<NB, 0, true>(rig, pb, fd, theta, st, fp, nullptr, nullptr, nullptr, argsBuf, stream);
   }
   if (dbgClk != nullptr) {
@@ -3815,10 +3785,10 @@ static hipError_t launchFusedNB(
     return launchFusedMode<NB, 1, false>(rig, pb, fd, theta, st, fp, dbgH, dbgG, dbgClk, argsBuf, stream);
   }
   if (pb.M == pb.rowsJoint) { // no parameter-space rows: the instantiations per step rule (kRule)
-    if (fp.stepRule == 0 && fp.doLineSearch == 0) {
+    if (fp.stepRule == MMX_STEP_GN_FIXED_LAMBDA && fp.doLineSearch == MMX_LINE_SEARCH_NONE) {
       return launchFusedMode<NB, 0, false, false, 0>(rig, pb, fd, theta, st, fp, nullptr, nullptr, nullptr, argsBuf, stream);
     }
-    if (fp.stepRule == 1) {
+    if (fp.stepRule == MMX_STEP_LM_SCHEDULE) {
       return launchFusedMode<NB, 0, false, false, 1>(rig, pb, fd, theta, st, fp, nullptr, nullptr, nullptr, argsBuf, stream);
     }
   }

@@ -906,15 +906,6 @@ size_t jointBlocksLdsBytes(int J, int P, int G) { // G = constraints of the bloc
 // =============================================================================================
 constexpr int kNeChunk = 32; // rows of J staged per step (16 when 32 rows of a very wide system do not fit the LDS)
 constexpr int kNeCols = 8; // columns of g per thread: n <= 256 * kNeCols = kMaxSolved (mmx_kernels.hpp)
-// a further refinement step is taken while |correction|^2 > kRefineTol2 |step|^2 (at most three steps)
-constexpr float kRefineTol2 = 1e-6f;
-// ... and a correction is only TAKEN when it is a contraction: |correction|^2 <= kRefineMax2 |step|^2, and not larger than
-// the correction before it.  With a well-conditioned factor the first correction is 1e-3 ... 1e-5 of the step; where the
-// fp32 factor is no preconditioner any more (pivots at rounding level: rank-deficient J with lambda ~ 1e-7) the
-// iteration d += M^-1 (g - A d) diverges -- measured in round 3: cfg2 at lambda = 1e-7 ended at a median error of 74 with
-// the unguarded refinement, 6 without any (the double solver: 5e-6 ... 16) -- so such a correction is undone and the
-// refinement stops.
-constexpr float kRefineMax2 = 0.25f;
 constexpr int kNeTilesPerThread = 4; // 4x4 tiles held per thread -> n <= 4*sqrt(2*256*4) ~ 180
 
 __global__ void __launch_bounds__(256) normalEquationsKernel(
@@ -1262,6 +1253,48 @@ size_t normalEquationsMfmaLdsBytes(int n) {
   return (2 * NP * kMfLd + 2 * kMfKc + T) * sizeof(float);
 }
 
+// theta -= delta (scatter to the full parameter space, gauss_newton_solver.cpp:254-257; with a line search or a damping
+// schedule the step is handed to stepUpdateKernel instead) and SolverT::solve's bookkeeping (solver.cpp:92-119)
+__device__ __forceinline__ void applyStepAndBook(
+    const ProblemDev& pb, int P, int b, const float* d0, bool badPivot, const double* errIter, float* theta, const SolveStateDev& st, const StepParams& sp, int tid) {
+  const int n = pb.n;
+  if (sp.delta != nullptr) {
+    for (int s2 = tid; s2 < n; s2 += 256) {
+      sp.delta[size_t(b) * n + s2] = d0[s2];
+    }
+    if (tid == 0) {
+      sp.stepIter[b] = sp.iteration + 1;
+    }
+  } else {
+    float* th = theta + size_t(b) * P;
+    for (int s2 = tid; s2 < n; s2 += 256) {
+      th[pb.enabledList[s2]] -= d0[s2];
+    }
+  }
+  if (sp.stepRule == MMX_STEP_TRUST_REGION) { // several linear solves per iteration: trustEndKernel books it once
+    if (tid == 0 && badPivot) {
+      st.status[b] |= MMX_SOLVE_NOT_PD;
+    }
+    return;
+  }
+  if (tid == 0) { // SolverT::solve bookkeeping (solver.cpp:92-119)
+    const double e = errIter[b];
+    const double last = st.lastError[b];
+    if (st.errorHistory != nullptr) {
+      st.errorHistory[size_t(b) * sp.maxIterations + sp.iteration] = e;
+    }
+    st.iterations[b] = sp.iteration + 1;
+    st.finalError[b] = e;
+    if (badPivot) { // a raw pivot was not positive; floored (kPivotFloor), the step taken
+      st.status[b] |= MMX_SOLVE_NOT_PD;
+    }
+    if (solveStops(sp.iteration, sp.minIterations, last, e, sp.threshold)) {
+      st.done[b] = 1;
+    }
+    st.lastError[b] = e;
+  }
+}
+
 // =============================================================================================
 // Kernel 3: dense GN step.  grid = B, block = 256, dynamic LDS = n*(n+1) + 3n + M + 4 floats.
 //   H diag += lambda ; L L^T = H ; d0 = solve(g)                 (gauss_newton_solver.cpp:248-251)
@@ -1408,7 +1441,7 @@ __global__ void __launch_bounds__(256) choleskyStepKernel(
     }
     lambdaF = fmaxf(lambda, kFactorDamping * waveReduceSumF(tr) / float(n > 0 ? n : 1));
     if (tid == 0 && lambdaF > lambda) {
-      st.status[b] |= 4; // MMX_SOLVE_DAMPING_FLOORED
+      st.status[b] |= MMX_SOLVE_DAMPING_FLOORED;
     }
   }
   for (int idx = tid; idx < n * n; idx += 256) {
@@ -1515,17 +1548,15 @@ __global__ void __launch_bounds__(256) choleskyStepKernel(
   }
   __syncthreads();
   const bool badPivot = *notPdPtr != 0;
-  constexpr bool bad = false; // (since the pivot floor the factorisation always completes; the reference never skips a step either)
+  // (since the pivot floor the factorisation always completes and the step is always taken; the reference never skips one either)
   MMX_SCLK(1)
-  if (!bad) {
-    triangularSolves(A, ld, n, d0, tid);
-  }
+  triangularSolves(A, ld, n, d0, tid);
   __syncthreads();
   MMX_SCLK(2)
   // up to three refinement steps: a further one only while the last correction exceeded 1e-3 of the
   // step (same rule as the fused kernel; one step is the normal case)
   float prevCorr2 = FLT_MAX;
-  for (int rf = 0; rf < sp.refine && !bad && n > 0; ++rf) {
+  for (int rf = 0; rf < sp.refine && n > 0; ++rf) {
     // w = r - J d0   (rows over threads, coalesced down each column)
     const float* Jb = jac + size_t(b) * size_t(M) * size_t(P);
     const float* rb = res + size_t(b) * size_t(M);
@@ -1596,7 +1627,7 @@ __global__ void __launch_bounds__(256) choleskyStepKernel(
     __syncthreads();
     const float corr2 = w[0] + w[1] + w[2] + w[3], step2 = w[4] + w[5] + w[6] + w[7];
     __syncthreads();
-    if (corr2 > kRefineMax2 * step2 || corr2 > prevCorr2) { // not a contraction: undo, stop (kRefineMax2)
+    if (refineUndo(corr2, step2, prevCorr2)) { // not a contraction
       for (int i = tid; i < n; i += 256) {
         d0[i] -= rho[i];
       }
@@ -1604,42 +1635,11 @@ __global__ void __launch_bounds__(256) choleskyStepKernel(
       break;
     }
     prevCorr2 = corr2;
-    if (!(corr2 > kRefineTol2 * step2)) {
+    if (!refineAgain(corr2, step2)) {
       break;
     }
   }
-  // theta -= delta (scatter to the full parameter space, gauss_newton_solver.cpp:254-257)
-  if (sp.delta != nullptr) { // line search / damping schedule: stepUpdateKernel applies the step
-    for (int s = tid; s < n; s += 256) {
-      sp.delta[size_t(b) * n + s] = bad ? 0.f : d0[s];
-    }
-    if (tid == 0) {
-      sp.stepIter[b] = bad ? -(sp.iteration + 1) : sp.iteration + 1;
-    }
-  } else if (!bad) {
-    float* th = theta + size_t(b) * P;
-    for (int s = tid; s < n; s += 256) {
-      th[pb.enabledList[s]] -= d0[s];
-    }
-  }
-  // SolverT::solve bookkeeping (solver.cpp:92-119)
-  if (tid == 0) {
-    const double e = errIter[b];
-    const double last = st.lastError[b];
-    if (st.errorHistory != nullptr) {
-      st.errorHistory[size_t(b) * sp.maxIterations + sp.iteration] = e;
-    }
-    st.iterations[b] = sp.iteration + 1;
-    st.finalError[b] = e;
-    if (badPivot) {
-      st.status[b] |= 2; // MMX_SOLVE_NOT_PD
-    }
-    const bool converged = fabs(last - e) / (fabs(e) + double(FLT_MIN)) <= double(sp.threshold) * double(FLT_EPSILON);
-    if (sp.iteration >= sp.minIterations && converged) {
-      st.done[b] = 1;
-    }
-    st.lastError[b] = e;
-  }
+  applyStepAndBook(pb, P, b, d0, badPivot, errIter, theta, st, sp, tid);
 }
 
 // =============================================================================================
@@ -2390,48 +2390,6 @@ __device__ __forceinline__ void tiledSweep(const float* __restrict__ L, int NB, 
   }
 }
 
-// theta -= delta (or the step handed to stepUpdateKernel) and SolverT::solve's bookkeeping (solver.cpp:92-119)
-__device__ __forceinline__ void applyStepAndBook(
-    const ProblemDev& pb, int P, int b, const float* d0, bool badPivot, const double* errIter, float* theta, const SolveStateDev& st, const StepParams& sp, int tid) {
-  const int n = pb.n;
-  if (sp.delta != nullptr) {
-    for (int s2 = tid; s2 < n; s2 += 256) {
-      sp.delta[size_t(b) * n + s2] = d0[s2];
-    }
-    if (tid == 0) {
-      sp.stepIter[b] = sp.iteration + 1;
-    }
-  } else {
-    float* th = theta + size_t(b) * P;
-    for (int s2 = tid; s2 < n; s2 += 256) {
-      th[pb.enabledList[s2]] -= d0[s2];
-    }
-  }
-  if (sp.stepRule == MMX_STEP_TRUST_REGION) { // several linear solves per iteration: trustEndKernel books it once
-    if (tid == 0 && badPivot) {
-      st.status[b] |= 2;
-    }
-    return;
-  }
-  if (tid == 0) { // SolverT::solve bookkeeping (solver.cpp:92-119)
-    const double e = errIter[b];
-    const double last = st.lastError[b];
-    if (st.errorHistory != nullptr) {
-      st.errorHistory[size_t(b) * sp.maxIterations + sp.iteration] = e;
-    }
-    st.iterations[b] = sp.iteration + 1;
-    st.finalError[b] = e;
-    if (badPivot) { // a raw pivot was not positive; floored (kPivotFloor), the step taken
-      st.status[b] |= 2;
-    }
-    const bool converged = fabs(last - e) / (fabs(e) + double(FLT_MIN)) <= double(sp.threshold) * double(FLT_EPSILON);
-    if (sp.iteration >= sp.minIterations && converged) {
-      st.done[b] = 1;
-    }
-    st.lastError[b] = e;
-  }
-}
-
 template <int kM> // 256-column slabs per thread: 2 (n <= 512, three workgroups per CU) or kNeCols (to kMaxSolved, one)
 __global__ void __launch_bounds__(256, kM == 2 ? 3 : 1) choleskyStepTiledKernel(
     ProblemDev pb,
@@ -2481,19 +2439,16 @@ __global__ void __launch_bounds__(256, kM == 2 ? 3 : 1) choleskyStepTiledKernel(
     }
     lambdaF = fmaxf(lambda, kFactorDamping * waveReduceSumF(tr) / float(n > 0 ? n : 1));
     if (tid == 0 && lambdaF > lambda) {
-      st.status[b] |= 4; // MMX_SOLVE_DAMPING_FLOORED
+      st.status[b] |= MMX_SOLVE_DAMPING_FLOORED;
     }
   }
   tiledFactor(jtj + size_t(b) * n * n, L, n, lambdaF, t, sp, b, tid, tclk);
   const bool badPivot = t.flags[0] != 0;
-  constexpr bool bad = false; // (pivot floor: the factorisation always completes, the step is always taken)
   MMX_SCLK(0) // (d0 is t.g: tiledFactor left y = L^-1 g there, behind its last barrier)
-  if (!bad) {
-    tiledSweep<false, false, kM>(L, NB, d0, tid);
-  }
+  tiledSweep<false, false, kM>(L, NB, d0, tid); // (pivot floor: the factorisation always completes, the step is always taken)
   MMX_SCLK(2)
   float prevCorr2 = FLT_MAX;
-  for (int rf = 0; rf < sp.refine && !bad; ++rf) { // see choleskyStepKernel
+  for (int rf = 0; rf < sp.refine; ++rf) { // see choleskyStepKernel
     const float* Jb = jac + size_t(b) * size_t(M) * size_t(P);
     const float* rb = res + size_t(b) * size_t(M);
     const bool vec4 = (M & 3) == 0 && (reinterpret_cast<uintptr_t>(jac) & 15) == 0;
@@ -2615,7 +2570,7 @@ __global__ void __launch_bounds__(256, kM == 2 ? 3 : 1) choleskyStepTiledKernel(
     __syncthreads();
     const float corr2 = wch[0] + wch[1] + wch[2] + wch[3], step2 = wch[4] + wch[5] + wch[6] + wch[7];
     __syncthreads();
-    if (corr2 > kRefineMax2 * step2 || corr2 > prevCorr2) { // not a contraction: undo, stop (kRefineMax2)
+    if (refineUndo(corr2, step2, prevCorr2)) { // not a contraction
       for (int i = tid; i < n; i += 256) {
         d0[i] -= rho[i];
       }
@@ -2623,7 +2578,7 @@ __global__ void __launch_bounds__(256, kM == 2 ? 3 : 1) choleskyStepTiledKernel(
       break;
     }
     prevCorr2 = corr2;
-    if (!(corr2 > kRefineTol2 * step2)) {
+    if (!refineAgain(corr2, step2)) {
       break;
     }
   }
@@ -2686,7 +2641,7 @@ __global__ void __launch_bounds__(256, 3) choleskyFactorTiledKernel(
     __syncthreads();
     const float lambdaFloor = kFactorDamping * ((t.rho[0] + t.rho[1]) + (t.rho[2] + t.rho[3])) / float(n > 0 ? n : 1);
     if (tid == 0 && lambdaFloor > lambda) {
-      st.status[b] |= 4; // MMX_SOLVE_DAMPING_FLOORED
+      st.status[b] |= MMX_SOLVE_DAMPING_FLOORED;
     }
     lambda = fmaxf(lambda, lambdaFloor);
   }
@@ -2710,14 +2665,11 @@ __global__ void __launch_bounds__(256, 3) choleskyFactorTiledKernel(
       atomicMax(reinterpret_cast<int*>(sp.diagAcc + 4 * size_t(b) + 3), __float_as_int(w)); // (this iteration's: the finish stage weights it with the step)
     }
   }
-  constexpr bool bad = false; // (pivot floor: the factorisation always completes, the step is always taken)
   float* d0 = t.g; // y = L^-1 g, solved in place
   MMX_SCLK(0)
-  if (!bad) {
-    tiledSweep<false, true>(L, NB, d0, tid, ml.row);
-  }
+  tiledSweep<false, true>(L, NB, d0, tid, ml.row); // (pivot floor: the factorisation always completes, the step is always taken)
   MMX_SCLK(2)
-  if (bad || !sp.refine) {
+  if (!sp.refine) {
     applyStepAndBook(pb, P, b, d0, badPivot, errIter, theta, st, sp, tid);
     if (tid == 0) {
       refState[b] = 1;
@@ -2730,7 +2682,7 @@ __global__ void __launch_bounds__(256, 3) choleskyFactorTiledKernel(
   if (tid == 0) {
     refState[b] = 0;
     if (badPivot) { // (the finish stage books the iteration; the floored pivot is reported from here)
-      st.status[b] |= 2;
+      st.status[b] |= MMX_SOLVE_NOT_PD;
     }
   }
 }
@@ -2902,7 +2854,7 @@ __global__ void __launch_bounds__(64 * kW, kW == 8 ? 4 : 2) choleskyFactorReside
     __syncthreads();
     const float lambdaFloor = kFactorDamping * ((red[0] + red[1]) + (red[2] + red[3])) / float(n > 0 ? n : 1);
     if (tid == 0 && lambdaFloor > lambda) {
-      st.status[b] |= 4; // MMX_SOLVE_DAMPING_FLOORED
+      st.status[b] |= MMX_SOLVE_DAMPING_FLOORED;
     }
     lambda = fmaxf(lambda, lambdaFloor);
     for (int i = tid; i < NP; i += 64 * kW) {
@@ -3094,7 +3046,7 @@ __global__ void __launch_bounds__(64 * kW, kW == 8 ? 4 : 2) choleskyFactorReside
   if (tid == 0) {
     refState[b] = 0;
     if (badPivot) { // (the finish stage books the iteration; the floored pivot is reported from here)
-      st.status[b] |= 2;
+      st.status[b] |= MMX_SOLVE_NOT_PD;
     }
   }
 }
@@ -3147,8 +3099,8 @@ __global__ void __launch_bounds__(256, 3) choleskyFinishTiledKernel(
   }
   __syncthreads();
   const float corr2 = sums[0] + sums[1] + sums[2] + sums[3], step2 = sums[4] + sums[5] + sums[6] + sums[7];
-  bool again = corr2 > kRefineTol2 * step2;
-  if (corr2 > kRefineMax2 * step2) { // not a contraction (kRefineMax2): undo this correction, the step is the one before it
+  bool again = refineAgain(corr2, step2);
+  if (refineDiverges(corr2, step2)) { // not a contraction: the step is the one before this correction (this stage does not compare with the round before)
     for (int i = tid; i < n; i += 256) {
       d0[i] -= rho[i];
     }
@@ -3213,21 +3165,8 @@ __global__ void __launch_bounds__(256) stepUpdateKernel(
       return;
     }
   } else {
-    const int mark = sp.stepIter[b];
-    if (mark != sp.iteration + 1 && mark != -(sp.iteration + 1)) {
+    if (sp.stepIter[b] != sp.iteration + 1) {
       return; // the instance had converged before this iteration
-    }
-    if (mark < 0) { // H was not positive definite: no step; the schedule raises the damping
-      if (sp.stepRule == MMX_STEP_LM_SCHEDULE && tid == 0) {
-        const float lam = sp.lambdaPer != nullptr ? sp.lambdaPer[b] : sp.lambda;
-        if (sp.stepHistory != nullptr) {
-          double* sh = sp.stepHistory + (size_t(b) * sp.maxIterations + sp.iteration) * 2;
-          sh[0] = double(lam);
-          sh[1] = -1.0; // no step was taken: the schedule treats it as a rejected one
-        }
-        sp.lambdaPer[b] = fminf(lam * sp.lmUp, sp.lmLambdaMax);
-      }
-      return;
     }
   }
   float lambda = sp.lambdaPer != nullptr ? sp.lambdaPer[b] : sp.lambda;
@@ -3299,14 +3238,9 @@ __global__ void __launch_bounds__(256) stepUpdateKernel(
     const float dn2 = (redT[0] + redT[1]) + (redT[2] + redT[3]), dg = (redT[4] + redT[5]) + (redT[6] + redT[7]);
     makeTrial(1.f);
     const double eNew = trialError();
-    const float predicted = dg + (lambda - 1e-20f) * dn2; // e - model (lambdaPer holds mu = 1e-20 + (lambda_TR - 1e-10))
-    const float rho = float((curError - eNew) / double(predicted));
-    float radius = sp.tr.radius[b];
-    if (rho < 0.25f) { // :256-262
-      radius = 0.25f * radius;
-    } else if (rho > 0.75f) {
-      radius = fminf(2.f * radius, 10.f);
-    }
+    const float predicted = trustPredicted(dg, lambda, dn2); // (lambdaPer holds mu = 1e-20 + (lambda_TR - 1e-10))
+    const float rho = gainRatio(curError, eNew, predicted);
+    const float radius = trustNextRadius(rho, sp.tr.radius[b], true); // (lambda_TR > 0 always holds: it starts at 1e-10)
     if (rho > 0.f) { // :265
       for (int i = tid; i < P; i += 256) {
         th[i] = thT[i];
@@ -3319,7 +3253,7 @@ __global__ void __launch_bounds__(256) stepUpdateKernel(
       } else {
         const int tried = sp.tr.step[b] + 1;
         sp.tr.step[b] = tried;
-        if (tried >= 10) { // :157: every trial rejected, the parameters stay (:268-269)
+        if (tried >= kTrustMaxTrials) {
           sp.tr.phase[b] = 3;
         } else { // the same step against the smaller radius: decide again (a Newton update of lambda follows)
           sp.tr.phase[b] = 1;
@@ -3343,7 +3277,7 @@ __global__ void __launch_bounds__(256) stepUpdateKernel(
     const float predicted = float((double(redF[0]) + double(redF[1])) + (double(redF[2]) + double(redF[3]))); // d.g + lambda d.d
     makeTrial(1.f);
     const double eNew = trialError();
-    const float rho = predicted > 0.f ? float((curError - eNew) / double(predicted)) : -1.f;
+    const float rho = lmGainRatio(curError, eNew, predicted);
     if (rho > 0.f) {
       for (int i = tid; i < P; i += 256) {
         th[i] = thT[i];
@@ -3355,18 +3289,13 @@ __global__ void __launch_bounds__(256) stepUpdateKernel(
         sh[0] = double(lambda);
         sh[1] = double(rho);
       }
-      if (!(rho >= 0.25f)) {
-        lambda = fminf(lambda * sp.lmUp, sp.lmLambdaMax);
-      } else if (rho > 0.75f) {
-        lambda = fmaxf(lambda * sp.lmDown, sp.lmLambdaMin);
-      }
-      sp.lambdaPer[b] = lambda;
+      sp.lambdaPer[b] = lmNextLambda(lambda, rho, sp.lmUp, sp.lmDown, sp.lmLambdaMin, sp.lmLambdaMax);
     }
     return;
   }
   const float scaledError = 1e-3f * float(curError);
   double gd = 0.0; // SubsetGaussNewtonSolverT / GaussNewtonSolverQRT rule: J^T r . delta
-  if (sp.doLineSearch == 2) {
+  if (sp.doLineSearch == MMX_LINE_SEARCH_DIRECTIONAL) {
     float part = 0.f;
     for (int c = tid; c < n; c += 256) {
       part += dl[c] * jtr[size_t(b) * n + c];
@@ -3382,7 +3311,7 @@ __global__ void __launch_bounds__(256) stepUpdateKernel(
   for (int ls = 0; ls < 10; ++ls) {
     makeTrial(scale);
     const double eNew = trialError();
-    if ((curError - eNew) >= (sp.doLineSearch == 2 ? double(1e-4f * scale) * gd : double(scale * scaledError))) {
+    if (armijoAccepts(sp.doLineSearch, curError, eNew, scale, scaledError, gd)) {
       break;
     }
     scale *= 0.5f;
@@ -3450,9 +3379,9 @@ __global__ void __launch_bounds__(256) trustDecideKernel(
   const float dn2 = (red[0] + red[1]) + (red[2] + red[3]), dg = (red[4] + red[5]) + (red[6] + red[7]);
   const int newton = sp.tr.newton[b];
   int next = 2; // the step is the one to try
-  if (newton == 0 && 2.f * dg < FLT_EPSILON * (1.f + float(errIter[b]))) { // :164 (gradientSub_ = 2 J^T r): not worth a step
+  if (trustGradientTooSmall(newton, dg, errIter[b])) {
     next = 3;
-  } else if (newton < 3 && sqrtf(dn2) >= 1.05f * sp.tr.radius[b]) { // :180-181
+  } else if (trustWantsNewton(newton, dn2, sp.tr.radius[b])) {
     const float* L = factor + size_t(b) * size_t(NB * (NB + 1) / 2) * 256;
     tiledSweep<true>(L, NB, x, tid, ml.col); // x = L^-1 p_l
     __syncthreads();
@@ -3467,10 +3396,9 @@ __global__ void __launch_bounds__(256) trustDecideKernel(
     }
     __syncthreads();
     const float q2 = (red[0] + red[1]) + (red[2] + red[3]);
-    if (q2 >= FLT_EPSILON) { // :198
-      const float pn = sqrtf(dn2), radius = sp.tr.radius[b];
-      const float deltaLambda = (dn2 / q2) * ((pn - radius) / radius);
-      if (deltaLambda > 0.f) { // :207: lambda only ever grows
+    if (trustNewtonDefined(q2)) {
+      const float deltaLambda = trustDeltaLambda(dn2, q2, sp.tr.radius[b]);
+      if (deltaLambda > 0.f) { // lambda only ever grows
         next = 0; // factor and solve again with the larger damping (the reference appends rows to its QR)
         if (tid == 0) {
           const float lam = sp.tr.lambda[b] + deltaLambda;
@@ -3500,8 +3428,7 @@ __global__ void trustEndKernel(SolveStateDev st, StepParams sp, const double* __
   }
   st.iterations[b] = sp.iteration + 1;
   st.finalError[b] = e;
-  const bool converged = fabs(last - e) / (fabs(e) + double(FLT_MIN)) <= double(sp.threshold) * double(FLT_EPSILON);
-  if (sp.iteration >= sp.minIterations && converged) {
+  if (solveStops(sp.iteration, sp.minIterations, last, e, sp.threshold)) {
     st.done[b] = 1;
   }
   st.lastError[b] = e;
@@ -3541,7 +3468,7 @@ __global__ void solveInitKernel(SolveStateDev st, int B, float* lambdaPer, float
     }
     st.done[b] = 0;
     st.iterations[b] = 0;
-    st.status[b] = 0;
+    st.status[b] = MMX_SOLVE_OK;
     st.lastError[b] = DBL_MAX; // solver.cpp:84-85
     st.finalError[b] = DBL_MAX;
   }
@@ -3569,9 +3496,9 @@ solveFinalizeKernel(float* __restrict__ theta, const float* __restrict__ thetaIn
     if (lane == 0) {
       const float* a = diagAcc + 4 * size_t(b);
       const float ratio = a[1] > 0.f ? kPivotFloorOrOne / a[1] : 1.f;
-      const float est = a[0] > 0.f ? kPrecisionGain * FLT_EPSILON * a[0] / kPivotFloorOrOne : kPrecisionGain * FLT_EPSILON / ratio;
-      if (!bad && st.precisionBound > 0.f && !(est <= st.precisionBound)) {
-        st.status[b] |= 8; // MMX_SOLVE_PRECISION_SUSPECT
+      const float est = a[0] > 0.f ? precisionEstimate(kPrecisionGain, a[0], kPivotFloorOrOne) : kPrecisionGain * FLT_EPSILON / ratio;
+      if (!bad && st.precisionBound > 0.f && precisionSuspect(est, st.precisionBound)) {
+        st.status[b] |= MMX_SOLVE_PRECISION_SUSPECT;
       }
       float* dg = st.diag + 4 * size_t(b);
       dg[0] = est;
@@ -3585,7 +3512,7 @@ solveFinalizeKernel(float* __restrict__ theta, const float* __restrict__ thetaIn
       th[i] = ti[i];
     }
     if (lane == 0) {
-      st.status[b] = 1; // MMX_SOLVE_NONFINITE
+      st.status[b] = MMX_SOLVE_NONFINITE;
     }
   }
 }

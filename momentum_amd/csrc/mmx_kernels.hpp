@@ -88,7 +88,7 @@ struct StepParams {
   // ---- line search / damping schedule of the explicit-Jacobian path: the Cholesky kernel leaves
   // the step in `delta` and stepUpdateKernel applies it (all null / 0: theta -= delta in place)
   float* delta; // [B][n] step of this iteration
-  int32_t* stepIter; // [B] iteration + 1 when `delta` holds a step, -(iteration + 1) when H was not positive definite
+  int32_t* stepIter; // [B] iteration + 1 when `delta` holds this iteration's step (an instance that had converged keeps an older mark)
   float* lambdaPer; // [B] per-instance damping (LM schedule, trust region) or null: `lambda` for everyone
   double* stepHistory; // SolveStateDev::stepHistory for stepUpdateKernel (which applies the schedule on the wide / explicit routes)
   float* diagErr0; // [B] with diagAcc: the first iteration's error (the estimate weights an iteration with sqrt(e_it / e_0))

@@ -625,24 +625,23 @@ __global__ void __launch_bounds__(kWaveThreads) waveSolveKernel(const WaveArgs a
           const bool mine = lane < n;
           const float corr2 = waveReduceSumF(mine ? cr * cr : 0.f);
           const float step2 = waveReduceSumF(mine ? dn * dn : 0.f);
-          // a correction is only taken when it is a contraction: otherwise undo it and stop
-          if (corr2 > 0.25f * step2 || corr2 > prevCorr2) {
+          if (refineUndo(corr2, step2, prevCorr2)) { // not a contraction
             dc = dn - cr;
             break;
           }
           dc = dn;
           prevCorr2 = corr2;
-          if (!(corr2 > 1e-6f * step2)) {
+          if (!refineAgain(corr2, step2)) {
             break;
           }
         }
       }
       // ================= K: update (gauss_newton_solver.cpp:283-313, gauss_newton_solver_qr.cpp:126-149)
       const int doLineSearch = waveArgs()->doLineSearch;
-      if (doLineSearch != 0) {
+      if (doLineSearch != MMX_LINE_SEARCH_NONE) {
         const float scaledError = 1e-3f * float(curError);
         double gd = 0.0;
-        if (doLineSearch == 2) {
+        if (doLineSearch == MMX_LINE_SEARCH_DIRECTIONAL) {
           gd = double(waveReduceSumF(lane < n ? gc * dc : 0.f));
         }
         float scale = 1.f;
@@ -657,7 +656,7 @@ __global__ void __launch_bounds__(kWaveThreads) waveSolveKernel(const WaveArgs a
           waveSync();
           waveFk(b, tr, js, lane);
           stateError = waveUnits(b, js, up, ur, us, lane);
-          if ((curError - stateError) >= (doLineSearch == 2 ? double(1e-4f * scale) * gd : double(scale * scaledError))) {
+          if (armijoAccepts(doLineSearch, curError, stateError, scale, scaledError, gd)) {
             break;
           }
           scale *= 0.5f;
@@ -687,13 +686,12 @@ __global__ void __launch_bounds__(kWaveThreads) waveSolveKernel(const WaveArgs a
           asGlobal(errorHistory)[row] = curError;
         }
         itersDone = it + 1;
-        status |= badPivot ? 2 : 0; // MMX_SOLVE_NOT_PD
-        status |= floored ? 4 : 0; // MMX_SOLVE_DAMPING_FLOORED
-        // solver.cpp:96-119
-        const bool converged = fabs(lastError - curError) / (fabs(curError) + double(FLT_MIN)) <= double(A->threshold) * double(FLT_EPSILON);
+        status |= badPivot ? MMX_SOLVE_NOT_PD : 0;
+        status |= floored ? MMX_SOLVE_DAMPING_FLOORED : 0;
+        const bool stop = solveStops(it, A->minIterations, lastError, curError, A->threshold);
         lastError = curError;
         asm volatile("" : "+v"(lastError)); // (kept in vector registers across the iteration: two scalar registers fewer)
-        if (it >= A->minIterations && converged) {
+        if (stop) {
           break;
         }
       }
@@ -725,7 +723,7 @@ __global__ void __launch_bounds__(kWaveThreads) waveSolveKernel(const WaveArgs a
     if (laneE == 0) {
       asGlobal(A->iterations)[b] = itersDone;
       asGlobal(A->finalError)[b] = curError;
-      asGlobal(A->status)[b] = anyBad ? 1 : status; // MMX_SOLVE_NONFINITE
+      asGlobal(A->status)[b] = solveStatus(anyBad, status);
     }
     if constexpr (kFrames) {
       if (++frame >= A->F) {
