@@ -1238,7 +1238,52 @@ __device__ __forceinline__ void panelRowUpdate1(float (&a)[16], int j) {
     a[c] -= a[j] * readLaneF(a[j], c);
   }
 }
+// The one-launch solve's form reads ALL 15 - j multipliers of a step into distinct SGPRs first and multiplies afterwards:
+// with one SGPR pair reused for every pair of columns the compiler put a hazard no-op between each pair of lane reads and
+// its v_pk_fma_f32 (about fifty per run of the chain, all on wave 0's dependent path).  The multipliers of columns
+// 16 - N .. 15 sit in one N-wide SGPR tuple, element c - (16 - N) for column c (an even column on an even register: the
+// pairs are the packed operands as they stand); the empty asm that takes the whole tuple as an INPUT is what keeps the reads
+// in front of the multiply-adds (a read-write operand costs an s_mov_b64 per pair).  The arithmetic -- pairing, the odd column's own v_fma_f32, operand order, negations -- is panelRowUpdate's.
+// Region 23 of the instruction census (scripts/probes/fused_census.sh): 1246 -> 1126 instructions, 185 -> 82 no-ops, the
+// floating-point instructions unchanged; every output bit-equal (profiles/r09_chain_records_ab.txt).
+// A/B build (momentum_amd/build.py): MMX_BUILD_VARIANT=chainoff compiles the chain as it was, panelRowUpdate's plain form.
+#ifndef MMX_EXP_CHAINOFF
+#define MMX_CHAIN_READS_FIRST 1
+#else
+#define MMX_CHAIN_READS_FIRST 0
+#endif
+template <int N>
+__device__ __forceinline__ void panelRowUpdateReadsFirst(float (&a)[16], int j) {
+  typedef float vNf __attribute__((ext_vector_type(N)));
+  constexpr int c0 = 16 - N;
+  vNf m; // (the elements left of column j + 1 stay unset: they are never read)
+#pragma unroll
+  for (int c = j + 1; c < 16; ++c) {
+    m[c - c0] = readLaneF(a[j], c);
+  }
+  asm volatile("" ::"s"(m));
+  if ((j & 1) == 0) {
+    a[j + 1] -= a[j] * m[j + 1 - c0];
+  }
+#pragma unroll
+  for (int c = (j + 2) & ~1; c < 16; c += 2) {
+    const v2f mlt{m[c - c0], m[c + 1 - c0]};
+    const v2f aj2{a[j], a[j]};
+    v2f acc{a[c], a[c + 1]};
+    acc = __builtin_elementwise_fma(-aj2, mlt, acc);
+    a[c] = acc.x, a[c + 1] = acc.y;
+  }
+}
 __device__ __forceinline__ void panelRowUpdate(float (&a)[16], int j) {
+#if MMX_CHAIN_READS_FIRST
+  if (j < 7) {
+    return panelRowUpdateReadsFirst<16>(a, j);
+  } else if (j < 11) {
+    return panelRowUpdateReadsFirst<8>(a, j);
+  } else if (j < 13) {
+    return panelRowUpdateReadsFirst<4>(a, j);
+  }
+#endif
   if ((j & 1) == 0) {
     a[j + 1] -= a[j] * readLaneF(a[j], j + 1);
   }

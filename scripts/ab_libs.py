@@ -9,7 +9,7 @@ windows).  Per shape: warm-up of every library, then THIS tree's library timed t
 counts as faster than the first one named (the baseline) when its median improvement exceeds twice the same-setting spread.
 The results of all libraries are compared bit for bit as well.  With a second copy of the baseline's file named <baseline>2
 (`--lib parent=a.so --lib parent2=copy_of_a.so`) the baseline-to-baseline spread is printed and this tree's library held to twice it.
-    python scripts/ab_libs.py --lib parent=<path to the parent tree's libmmx_hip.so> [--lib name=path ...] [--out file]
+    python scripts/ab_libs.py --lib parent=<path to the parent tree's libmmx_hip.so> [--lib name=path ...] [--shapes N] [--out file]
 """
 import argparse
 import os
@@ -30,6 +30,7 @@ ap.add_argument("--lib", action="append", default=[], metavar="NAME=PATH", help=
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--shapes", type=int, default=0, help="only the first N shapes (0: all)")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ab_libs.txt"))
 args = ap.parse_args()
 assert args.steps >= 30 and args.rounds >= 3 and args.lib
@@ -80,7 +81,7 @@ def window(db, opt, steps):
 
 
 say(f"library A/B, one process, {args.steps} solves per window, {args.rounds} rounds over {' / '.join(LIBS)}; device: {torch.cuda.get_device_name(0)}")
-for name, cfg, B, rule, ls, lam, prec, share in SHAPES:
+for name, cfg, B, rule, ls, lam, prec, share in SHAPES[: args.shapes or None]:
     steps = max(1, args.steps // share)
     rig, parents, _, _, _ = bench.build_rig(cfg)
     opt = GnOptions.make(min_iterations=10, max_iterations=10, threshold=1.0, regularization=lam, step_rule=rule, do_line_search=ls, precision=prec)
