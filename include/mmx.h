@@ -596,6 +596,12 @@ int32_t mmx_problem_last_route(const mmx_problem* problem);
 /* The joint count the solve kernels named under mmx_tuning::joint_pruning run over with the problem's current tables and
  * tuning: the live joints, or mmx_rig_num_joints when nothing is pruned.  (Additive, host-side query.) */
 int32_t mmx_problem_num_solve_joints(const mmx_problem* problem);
+/* Which form of the double kernel mmx_solve_f64 (MMX_PRECISION_F64, the last stage of MMX_PRECISION_AUTO) would launch for the
+ * problem's current tables: *resident = 1 when packed H and a chunk of J stay in LDS, 0 for the form that keeps J and H in the
+ * problem's global scratch; *chunk_rows = the rows of J that form assembles per chunk.  Either output may be null.  No GPU
+ * work, no allocation.  MMX_ERR_UNSUPPORTED where mmx_solve_f64 would refuse the rig (beyond the kernel's LDS budget).
+ * (Additive, host-side query.) */
+int32_t mmx_problem_f64_form(const mmx_problem* problem, int32_t* resident, int32_t* chunk_rows);
 
 /* M = 3*Kp + 9*Ko + rows of the further blocks and parameter-space blocks
  * (JointErrorFunctionT::getJacobianSize, joint_error_function-inl.h:300-302). */

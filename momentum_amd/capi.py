@@ -26,7 +26,7 @@ SYMBOLS = [
     "mmx_gn_options_default", "mmx_abi_version", "mmx_last_error", "mmx_device_count",
     "mmx_rig_create", "mmx_rig_destroy", "mmx_rig_num_joints", "mmx_rig_num_params",
     "mmx_problem_create", "mmx_problem_destroy", "mmx_problem_num_rows", "mmx_problem_batch",
-    "mmx_problem_set_tuning", "mmx_problem_last_route", "mmx_problem_num_solve_joints",
+    "mmx_problem_set_tuning", "mmx_problem_last_route", "mmx_problem_num_solve_joints", "mmx_problem_f64_form",
     "mmx_problem_set_enabled", "mmx_problem_set_constraints", "mmx_problem_set_constraints_sized", "mmx_problem_set_instance_rig", "mmx_problem_set_instance_parents", "mmx_eval_jacobian", "mmx_eval_jacobian_timed", "mmx_debug_store_pattern",
     "mmx_eval_skeleton_state", "mmx_eval_normal_equations", "mmx_solve", "mmx_solve_with_history", "mmx_solve_with_step_history", "mmx_problem_solve_diagnostics", "mmx_solve_f64", "mmx_solve_f64_host", "mmx_solve_host",
     "mmx_solve_frames", "mmx_solve_frames_host",
@@ -76,6 +76,7 @@ def lib() -> C.CDLL:
     L.mmx_problem_set_tuning.argtypes = [vp, C.POINTER(_abi.Tuning)]
     L.mmx_problem_last_route.argtypes = [vp]
     L.mmx_problem_num_solve_joints.argtypes = [vp]
+    L.mmx_problem_f64_form.argtypes = [vp, _abi.c_int32_p, _abi.c_int32_p]
     L.mmx_problem_set_constraints.argtypes = [vp, C.POINTER(ConstraintData), vp]
     L.mmx_problem_set_constraints_sized.argtypes = [vp, C.POINTER(ConstraintData), C.c_size_t, vp]
     L.mmx_problem_set_instance_rig.argtypes = [vp, vp, vp, i32, vp]
@@ -337,6 +338,12 @@ class Problem:
     def num_solve_joints(self) -> int:
         """Joints the solve kernels run over (mmx_problem_num_solve_joints): the live ones, or all when nothing is pruned."""
         return int(lib().mmx_problem_num_solve_joints(self._h))
+
+    def f64_form(self):
+        """(resident, chunk_rows) of the double kernel mmx_solve_f64 would launch for the current tables (mmx_problem_f64_form)."""
+        res, rows = C.c_int32(0), C.c_int32(0)
+        _check(lib().mmx_problem_f64_form(self._h, C.byref(res), C.byref(rows)))
+        return bool(res.value), int(rows.value)
 
     def last_route(self) -> str:
         r = int(lib().mmx_problem_last_route(self._h))

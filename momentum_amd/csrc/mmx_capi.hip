@@ -2234,6 +2234,28 @@ int32_t mmx_solve_f64(
   return runDouble(pb, o, theta_dev, out, mmx::F64Select{nullptr, nullptr, nullptr, nullptr}, static_cast<hipStream_t>(stream));
 }
 
+int32_t mmx_problem_f64_form(const mmx_problem* pb, int32_t* resident, int32_t* chunk_rows) {
+  if (pb == nullptr || pb->rig == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "problem handle is null");
+  }
+  mmx_gn_options o;
+  mmx_gn_options_default(&o);
+  const mmx::SolvePlan plan = mmx::planSolveF64(solveFacts(pb, SolveOutputs{}, MMX_PRECISION_F64, false), o);
+  if (plan.code != MMX_OK) {
+    return fail(plan.code, plan.message);
+  }
+  // (the arguments of residentF64 and launchSolveF64)
+  const int J = pb->rig->J, P = pb->rig->P, G = pb->dev.G + pb->dev.NE, genRows = pb->dev.rowsJoint - 3 * pb->U;
+  const bool res = residentF64(pb);
+  if (resident != nullptr) {
+    *resident = res ? 1 : 0;
+  }
+  if (chunk_rows != nullptr) {
+    *chunk_rows = res ? mmx::solveF64ResidentChunkRows(J, P, pb->U, pb->solveN, G, genRows) : mmx::solveF64ChunkRows(J, P, pb->U, pb->solveN, G, genRows);
+  }
+  return MMX_OK;
+}
+
 int32_t mmx_debug_fused_normal_equations(
     mmx_problem* pb,
     const float* theta_dev,

@@ -742,7 +742,8 @@ __device__ __forceinline__ double rsqrtNewton(double v) {
 // it -- and the sixteen column steps run without a barrier; the rank-16 trailing update is four v_mfma_f64_16x16x4_f64 per
 // 16 x 16 tile.  Three barriers per panel (n / 16 panels) where the four-column form took three per four columns: the
 // factor of a 96-parameter system went from 173 k to ~45 k cycles.  Column-packed storage makes "a lane = a row" reads
-// consecutive in LDS.  Rows covered per panel: 16 + 192 (the resident form is taken up to n = 208).  True when a pivot was
+// consecutive in LDS.  Rows covered per panel: 16 + 192 (solveF64ResidentChunkRows admits n <= 208; its LDS budget ends the
+// resident form sooner -- the packed H of n = 208 alone is 174 KB).  True when a pivot was
 // not positive (nothing of that panel is written).
 // With rhs (and the work vectors w1, w2) the forward substitution L y = rhs rides along, y in w2: the rows of a panel are
 // in registers when its block of y is known, so taking the block out of the right-hand sides below costs no further read
@@ -949,7 +950,8 @@ __device__ __noinline__ void residentBackward(const ldsd* H, const ldsd* invd, l
 // LDS, factored by a right-looking blocked Cholesky (four columns per barrier pair) and solved by blocked substitutions
 // (one barrier per four unknowns), all in double.  Same arithmetic per entry as the scratch form below it (sums over the
 // rows in a different grouping: parity with the oracle's double run stays at the 1e-10 the tests hold).  Taken when the
-// packed H and a chunk of at least twelve rows fit a workgroup's LDS (n <= ~180 solved parameters); the scratch form
+// packed H and a chunk of at least twelve rows fit a workgroup's LDS (mmx_problem_f64_form tells: n <= 160 on the 219-parameter humanoid with every joint constrained,
+// n <= 64 on the 300-joint rig; tests/test_gpu_f64_forms.py); the scratch form
 // (J and H in a global scratch of the problem) is kept for the systems beyond.
 template <bool kRes>
 __global__ void __launch_bounds__(256, kRes ? 2 : 1) solveF64Kernel(
@@ -1812,7 +1814,7 @@ static size_t solveF64BaseDoubles(int J, int P, int U, int n, int G, int genRows
 }
 // rows of J staged per chunk: as many as fit next to the fixed part (at most 64, at least 4), leaving room for two
 // workgroups per CU when the system is small
-static int solveF64ChunkRows(int J, int P, int U, int n, int G, int genRows) {
+int solveF64ChunkRows(int J, int P, int U, int n, int G, int genRows) {
   const size_t base = solveF64BaseDoubles(J, P, U, n, G, genRows) * sizeof(double);
   const size_t budget = base < 60 * 1024 ? 78 * 1024 : 158 * 1024;
   if (base + size_t(n > 0 ? n : 1) * 5 * sizeof(double) > budget) {

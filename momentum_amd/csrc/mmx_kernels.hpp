@@ -255,6 +255,8 @@ size_t solveF64LdsBytes(int J, int P, int U, int n, int G = 0, int genRows = 0);
 bool solveF64IsResident(int J, int P, int U, int n, int G = 0, int genRows = 0); // the system stays in LDS: no J / H scratch is read or written
 // rows of J the resident form assembles per chunk (a multiple of twelve; 0: the scratch form runs)
 int solveF64ResidentChunkRows(int J, int P, int U, int n, int G = 0, int genRows = 0);
+// rows of J the scratch form stages per chunk (at most 64; below 4 it does not fit)
+int solveF64ChunkRows(int J, int P, int U, int n, int G = 0, int genRows = 0);
 // The resident form's assembly list (batch-shared, iteration-invariant; built on the host, mmx_capi.hip): per chunk of
 // units the entries (column, unit) of J that have an applicable source at all -- one in six on the 72-joint rig -- each
 // with the indices of those sources in the kernel's packed source table.  groups[g] = {column | unit-in-chunk << 12 |
