@@ -878,6 +878,51 @@ int32_t mmx_eval_gradient(mmx_problem* problem, const float* theta_dev, float* g
 int32_t mmx_eval_gradient_host(mmx_problem* problem, const float* theta_host, float* grad_host, double* err_host);
 
 /*
+ * The backward pass of mmx_eval_skeleton_state: the vector-Jacobian product of the skeleton state with a caller-supplied
+ * cotangent, in O(joints + entries of the parameter transform) per instance through the skeleton tree (the adjoint pass of
+ * mmx_eval_gradient with JOINTS as the units).  No state Jacobian (8 J x P) is formed.  The counterpart of _backward_kernel
+ * in pymomentum/backend/triton_fk.py.  Added without an ABI bump (no struct grows): a library that predates the functions
+ * lacks the symbols -- that is the feature probe.
+ *   meaning     with state [B][J][8] = (tx,ty,tz, qx,qy,qz,qw, s) as mmx_eval_skeleton_state returns it for this handle at
+ *               theta_dev, and L any scalar function of it:
+ *                 state_grad_dev [B][J][8]  dL/dstate, in the layout of the state
+ *                 theta_grad_dev [B][P]     dL/dtheta[b][p] = sum_{j,c} state_grad[b][j][c] dstate[b][j][c]/dtheta[b][p]
+ *               The kernel recomputes the forward kinematics (the solve kernels': pointer-jumping rounds in double), so
+ *               nothing has to be kept from a forward call.  It renormalises every local quaternion in double before the
+ *               rounds: the exact composition of single-precision rotations lets the world quaternion's norm drift by up
+ *               to 1e-6 down a long chain, which the state tolerates and a derivative of it does not; the state the
+ *               derivative is taken at differs from the returned one by that drift.  Per-instance offsets and pre-rotations
+ *               (mmx_problem_set_instance_rig) are read; the derivative is with respect to theta only.
+ *   written     all P entries of every row.  A parameter without an entry in the parameter transform gets an exact zero.
+ *               The enabled mask is NOT read (the forward does not read it either: a disabled parameter gets its true
+ *               derivative), and joint pruning does not apply (every joint's state is an output).  Constraints are not read.
+ *   quaternion  the cotangent is applied to the quaternion as the forward returns it: the same sign, and no
+ *               renormalisation term of its own.  The state's quaternions are products of unit rotations, so the component
+ *               of state_grad's quaternion part along q itself contributes nothing.
+ *   refusals    before any output is touched: MMX_ERR_INVALID_ARGUMENT for a null pointer; MMX_ERR_UNSUPPORTED, with a
+ *               message that names the condition, for a rig whose tables exceed the kernel's LDS budget (160 KB: beyond
+ *               about 700 joints).  Every rig the one-launch solve takes is inside.
+ *   determinism a row of the result depends on that instance's inputs only -- not on the batch size, the instance's
+ *               position in the batch, or the run (no floating-point atomics; every entry is summed by one thread in a
+ *               fixed order).
+ * One kernel is enqueued on `stream` and the call returns (no memset node, no stream wait, no host read).  The rig-level
+ * tables are built and uploaded by the first call on a rig: that call is the warm-up, after it the call can be captured into
+ * a HIP graph like the other entry points.  The _host form copies in, runs, copies out and synchronises like the other host
+ * wrappers.
+ */
+int32_t mmx_eval_skeleton_state_backward(
+    mmx_problem* problem,
+    const float* theta_dev,
+    const float* state_grad_dev,
+    float* theta_grad_dev,
+    void* stream);
+int32_t mmx_eval_skeleton_state_backward_host(
+    mmx_problem* problem,
+    const float* theta_host,
+    const float* state_grad_host,
+    float* theta_grad_host);
+
+/*
  * Numerical diagnostics of the LAST single-precision solve on this handle (one-launch and wide routes;
  * MMX_ERR_UNSUPPORTED after a solve on the explicit-Jacobian route or before the first solve): diag_dev [B][4] floats
  *   [0] the precision estimate MMX_SOLVE_PRECISION_SUSPECT is decided on (relative to |theta|)

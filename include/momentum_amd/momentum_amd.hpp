@@ -802,6 +802,24 @@ class BatchedSkeletonState {
       }
     }
   }
+  // The backward pass of set(): with stateGradient [batch][numJoints][8] = dL/d(tx,ty,tz, qx,qy,qz,qw, s) of every joint's
+  // world transform at modelParameters, returns dL/dmodelParameters [batch * numParameters] (mmx_eval_skeleton_state_backward:
+  // through the skeleton tree, no state Jacobian).  The quaternion part is applied to the rotation as set() returns it.
+  static std::vector<float> backward(
+      BatchedSkeletonSolverFunction& function, const std::vector<float>& modelParameters, const std::vector<float>& stateGradient) {
+    function.sync();
+    const size_t B = function.batchSize(), P = function.getNumParameters();
+    if (modelParameters.size() != B * P) {
+      throw std::runtime_error("momentum_amd: parameters.size() != batch * numParameters");
+    }
+    const size_t J = size_t(mmx_rig_num_joints(function.character().handle()));
+    if (stateGradient.size() != B * J * 8) {
+      throw std::runtime_error("momentum_amd: stateGradient.size() != batch * numJoints * 8");
+    }
+    std::vector<float> grad(B * P);
+    check(mmx_eval_skeleton_state_backward_host(function.handle(), modelParameters.data(), stateGradient.data(), grad.data()));
+    return grad;
+  }
   size_t batchSize() const {
     return states_.size();
   }

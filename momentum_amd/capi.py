@@ -31,6 +31,7 @@ SYMBOLS = [
     "mmx_eval_skeleton_state", "mmx_eval_normal_equations", "mmx_solve", "mmx_solve_with_history", "mmx_solve_with_step_history", "mmx_problem_solve_diagnostics", "mmx_solve_f64", "mmx_solve_f64_host", "mmx_solve_host",
     "mmx_solve_frames", "mmx_solve_frames_host",
     "mmx_eval_gradient", "mmx_eval_gradient_host",
+    "mmx_eval_skeleton_state_backward", "mmx_eval_skeleton_state_backward_host",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
     "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
@@ -97,6 +98,8 @@ def lib() -> C.CDLL:
     L.mmx_solve_frames_host.argtypes = [vp, C.POINTER(GnOptions), i32, vp, vp, vp, vp]
     L.mmx_eval_gradient.argtypes = [vp, vp, vp, vp, vp]
     L.mmx_eval_gradient_host.argtypes = [vp, vp, vp, vp]
+    L.mmx_eval_skeleton_state_backward.argtypes = [vp, vp, vp, vp, vp]
+    L.mmx_eval_skeleton_state_backward_host.argtypes = [vp, vp, vp, vp]
     L.mmx_eval_jacobian_host.argtypes = [vp, vp, vp, vp, vp, i32]
     L.mmx_eval_skeleton_state_host.argtypes = [vp, vp, vp]
     L.mmx_debug_tree_normal_equations.argtypes = [vp, vp, vp, vp, vp]
@@ -526,6 +529,22 @@ class Problem:
         st = torch.empty((self.B, self.J, 8), dtype=torch.float32, device=self.device)
         _check(lib().mmx_eval_skeleton_state(self._h, _dev(theta), _dev(st), _stream_ptr()))
         return st
+
+    # -- the backward pass of skeleton_state (mmx_eval_skeleton_state_backward)
+    def skeleton_state_backward(self, theta, state_grad, out=None):
+        """Returns dL/dtheta [B,P] float32 for state_grad = dL/dstate [B,J,8] (the layout skeleton_state returns), through the
+        skeleton tree without a state Jacobian.  Every entry is written; the enabled mask and the constraints are not read.
+        Raises MmxError (MMX_ERR_UNSUPPORTED) for a rig beyond the kernel's LDS budget."""
+        import torch
+
+        theta = self._theta(theta)
+        assert isinstance(state_grad, torch.Tensor) and state_grad.is_cuda and state_grad.dtype == torch.float32
+        assert state_grad.is_contiguous() and tuple(state_grad.shape) == (self.B, self.J, 8), state_grad.shape
+        if out is None:
+            out = torch.empty((self.B, self.P), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (self.B, self.P), out.shape
+        _check(lib().mmx_eval_skeleton_state_backward(self._h, _dev(theta), _dev(state_grad), _dev(out), _stream_ptr()))
+        return out
 
     def normal_equations(self, theta):
         import torch

@@ -17,6 +17,7 @@
 #include <new>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -208,6 +209,12 @@ struct mmx_rig {
   mmx::HostTables topo; // built with all parameters enabled
   DevBuf dParent, dPreRot, dOffset, dPtOuter, dPtInner, dPtValue, dPtOffsets, dLevelOrder, dLevelStart, dPtEll, dJumpParent, dPtRowRec;
   mmx::RigDev dev{};
+  // mmx_eval_skeleton_state_backward's tables (mmx::buildStateBackwardTables): built from `topo` and uploaded by the first
+  // call on the rig, then kept -- they depend on the rig alone
+  std::mutex sbMutex;
+  bool sbReady = false;
+  DevBuf dSbSubSize, dSbLoadedPos, dSbJointPos, dSbColStart, dSbColSources;
+  mmx::StateBackwardDev sbDev{};
 
   mmx_rig_desc desc() const {
     mmx_rig_desc d{};
@@ -2430,6 +2437,66 @@ int32_t mmx_eval_skeleton_state_host(mmx_problem* pb, const float* theta_host, f
   MMX_TRY(mmx_eval_skeleton_state(pb, pb->sTheta.as<float>(), pb->sRes.as<float>(), nullptr));
   MMX_HIP(hipDeviceSynchronize());
   MMX_HIP(hipMemcpy(state_host, pb->sRes.p, B * J * 8 * sizeof(float), hipMemcpyDeviceToHost));
+  return MMX_OK;
+}
+
+namespace {
+// The rig's tables of the backward pass, on the device: built and uploaded by the first call (the warm-up), kept afterwards
+int32_t ensureStateBackwardTables(mmx_rig* rig) {
+  static_assert(sizeof(mmx::ColumnSource) == sizeof(mmx::ColumnSourceDev), "ColumnSource layouts must match");
+  std::lock_guard<std::mutex> lock(rig->sbMutex);
+  if (rig->sbReady) {
+    return MMX_OK;
+  }
+  const mmx::StateBackwardTables t = mmx::buildStateBackwardTables(rig->topo);
+  MMX_HIP(upload(rig->dSbSubSize, t.subSize));
+  MMX_HIP(upload(rig->dSbLoadedPos, t.loadedPos));
+  MMX_HIP(upload(rig->dSbJointPos, t.jointPos));
+  MMX_HIP(upload(rig->dSbColStart, t.colStart));
+  MMX_HIP(upload(rig->dSbColSources, t.colSources));
+  mmx::StateBackwardDev& d = rig->sbDev;
+  d.subSize = rig->dSbSubSize.as<int32_t>();
+  d.loadedPos = rig->dSbLoadedPos.as<int32_t>();
+  d.jointPos = rig->dSbJointPos.as<int32_t>();
+  d.colStart = rig->dSbColStart.as<int32_t>();
+  d.colSources = rig->dSbColSources.as<mmx::ColumnSourceDev>();
+  rig->sbReady = true;
+  return MMX_OK;
+}
+} // namespace
+
+int32_t mmx_eval_skeleton_state_backward(mmx_problem* pb, const float* theta_dev, const float* state_grad_dev, float* theta_grad_dev, void* stream) {
+  MMX_ZONE("mmx_eval_skeleton_state_backward (skeleton state VJP)");
+  MMX_TRY(checkProblem(pb, false));
+  if (theta_dev == nullptr || state_grad_dev == nullptr || theta_grad_dev == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_eval_skeleton_state_backward: theta / state_grad / theta_grad is null");
+  }
+  // the scope rule is host code of its own (mmx_solve_plan.cpp): a refusal comes before any output is touched
+  if (const char* why = mmx::stateBackwardRefusal(mmx::stateBackwardLdsBytes(pb->rig->J, pb->rig->P))) {
+    return fail(MMX_ERR_UNSUPPORTED, why);
+  }
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  MMX_TRY(ensureStateBackwardTables(pb->rig));
+  MMX_HIP(mmx::launchStateBackward(pb->rigDev, pb->rig->sbDev, pb->B, theta_dev, state_grad_dev, theta_grad_dev, static_cast<hipStream_t>(stream)));
+  return MMX_OK;
+}
+
+int32_t mmx_eval_skeleton_state_backward_host(mmx_problem* pb, const float* theta_host, const float* state_grad_host, float* theta_grad_host) {
+  MMX_ZONE("mmx_eval_skeleton_state_backward_host");
+  MMX_TRY(checkProblem(pb, false));
+  if (theta_host == nullptr || state_grad_host == nullptr || theta_grad_host == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_eval_skeleton_state_backward_host: theta / state_grad / theta_grad is null");
+  }
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P), J = size_t(pb->rig->J);
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  MMX_HIP(pb->sTheta.ensure(B * P * sizeof(float)));
+  MMX_HIP(pb->sRes.ensure(B * J * 8 * sizeof(float)));
+  MMX_HIP(pb->sJtr.ensure(B * P * sizeof(float)));
+  MMX_HIP(hipMemcpy(pb->sTheta.p, theta_host, B * P * sizeof(float), hipMemcpyHostToDevice));
+  MMX_HIP(hipMemcpy(pb->sRes.p, state_grad_host, B * J * 8 * sizeof(float), hipMemcpyHostToDevice));
+  MMX_TRY(mmx_eval_skeleton_state_backward(pb, pb->sTheta.as<float>(), pb->sRes.as<float>(), pb->sJtr.as<float>(), nullptr));
+  MMX_HIP(hipDeviceSynchronize());
+  MMX_HIP(hipMemcpy(theta_grad_host, pb->sJtr.p, B * P * sizeof(float), hipMemcpyDeviceToHost));
   return MMX_OK;
 }
 

@@ -353,7 +353,12 @@ __device__ __forceinline__ void csrRowsFromRecords(const int4* rec, int numRec, 
 // of all joints at once (parameter_transform.cpp:110-124, joint_state.cpp:44-62), world transforms
 // by pointer jumping (skeleton_state.cpp:100-121 re-associated), optionally the rotation axes.
 // Ends with a barrier.  Clobbers alt / jlA / jlB (assembly scratch = the Cholesky region).
-template <bool kGlobalTables = false, int kT = 256> // the rig's CSR tables are read from global memory (prefetching walk); kT threads
+// kUnitLocal (the skeleton state's backward pass only; the solves and the forward keep false and their code): every local
+// quaternion is renormalised in double before the composition.  A single-precision local quaternion has |q_l| = 1 +- 5e-8 and
+// the rounds compose exactly, so the world quaternion's norm is the PRODUCT of the local norms (1 - 8e-7 fifteen joints down
+// an all-dof chain); a quaternion of norm rho turns v into (1 - rho^2) v + rho^2 R v, which puts 1 - rho^2 on every lever arm
+// and axis below -- invisible to a solve at 1e-5, ten times the rounding of a derivative of the state.
+template <bool kGlobalTables = false, int kT = 256, bool kUnitLocal = false> // the rig's CSR tables are read from global memory (prefetching walk); kT threads
 __device__ __forceinline__ void
 blockFk(const RigView& rig, const FusedLds& s, const float* th, int tid, bool withAxes, long long* clk = nullptr, long long* clkLast = nullptr) {
   auto stamp = [&](int slot) { // profiling aid (MMX_PHASE_CLOCKS): sub-phases of FK
@@ -407,7 +412,21 @@ blockFk(const RigView& rig, const FusedLds& s, const float* th, int tid, bool wi
     } else {
       fkLocalFromParams(s.jd + 7 * j, rig.preRot + 4 * j, rig.offset + 3 * j, loc, slot + 8);
     }
-    if (rig.jumpRounds == 0) { // every joint is a root
+    if (kUnitLocal) {
+      const double qx = loc[3], qy = loc[4], qz = loc[5], qw = loc[6];
+      const double inv = 1.0 / sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
+      if (rig.jumpRounds == 0) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          slot[c] = c >= 3 && c < 7 ? float(double(loc[c]) * inv) : loc[c];
+        }
+      } else {
+        FkXf x;
+        x.tx = loc[0], x.ty = loc[1], x.tz = loc[2], x.qx = qx * inv, x.qy = qy * inv, x.qz = qz * inv, x.qw = qw * inv;
+        x.s = loc[7], x.jl = rig.parent[j] + 1;
+        fkStoreD(s.fkA, Jp, j, x);
+      }
+    } else if (rig.jumpRounds == 0) { // every joint is a root
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         slot[c] = loc[c];

@@ -245,6 +245,23 @@ int32_t buildHostTables(const mmx_rig_desc* d, const uint8_t* enabled, HostTable
   return MMX_OK;
 }
 
+StateBackwardTables buildStateBackwardTables(const HostTables& t) {
+  StateBackwardTables s;
+  const int32_t J = t.J;
+  s.dfsJoint.assign(size_t(J), 0);
+  s.subSize.assign(size_t(J), 1);
+  s.loadedPos.resize(size_t(J));
+  for (int32_t j = 0; j < J; ++j) {
+    s.dfsJoint[size_t(t.tin[size_t(j)])] = j;
+    s.subSize[size_t(t.tin[size_t(j)])] = t.tout[size_t(j)] - t.tin[size_t(j)];
+    s.loadedPos[size_t(j)] = j;
+  }
+  s.jointPos = t.tin;
+  s.colStart = t.colStart; // (every parameter enabled: no entry of the transform was dropped)
+  s.colSources = t.colSources;
+  return s;
+}
+
 int32_t buildFusedTables(
     const mmx_rig_desc* d,
     const HostTables& t,

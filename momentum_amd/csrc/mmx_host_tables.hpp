@@ -165,6 +165,20 @@ int32_t validateRigDesc(const mmx_rig_desc* d, std::string& err);
 // Builds all tables.  `enabled` may be null (= all parameters enabled).
 int32_t buildHostTables(const mmx_rig_desc* d, const uint8_t* enabled, HostTables& out, std::string& err);
 
+// Tables of mmx_eval_skeleton_state_backward, from the rig alone (no constraint, no enabled mask): the joints in DFS
+// pre-order with their subtree sizes, EVERY position as a loaded one (each joint's state is an output and carries a
+// cotangent), and per model parameter the sources of ALL its transform entries in row order -- colStart / colSources of
+// buildHostTables with every parameter enabled, taken over as they are.  Built once per rig and never by a constraint update.
+struct StateBackwardTables {
+  std::vector<int32_t> dfsJoint; // [J] joint at DFS position k
+  std::vector<int32_t> subSize; // [J] subtree size of the joint at DFS position k
+  std::vector<int32_t> loadedPos; // [J] 0 .. J-1
+  std::vector<int32_t> jointPos; // [J] DFS position of joint j (= tin)
+  std::vector<int32_t> colStart; // [P+1]
+  std::vector<ColumnSource> colSources;
+};
+StateBackwardTables buildStateBackwardTables(const HostTables& allEnabled);
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Problem tables.  Everything below is what mmx_capi.hip uploads for a problem (uploadProblemTables, uploadSolveView): the
 // upload path gathers a ProblemTopology from its handle, calls these builders and copies the vectors to the device.  One

@@ -220,6 +220,19 @@ hipError_t launchTreeRefine(
 // may be null (not both): without grad the moments, tree sums and gather are skipped.
 size_t gradientLdsBytes(int J, int P, int U);
 hipError_t launchEvalGradient(const RigDev& rig, const ProblemDev& pb, const FusedDev& fd, const float* theta, float* grad, double* err, hipStream_t stream);
+// mmx_eval_skeleton_state_backward (mmx_state_backward.hip): thetaGrad[b][p] = sum over the state entries of stateGrad x
+// d state / d theta_p, through the tree with the joints as units; one 256-thread workgroup per instance, one kernel node.
+// The tables are the rig's alone (mmx_host_tables.hpp buildStateBackwardTables): no constraint, no enabled mask.
+struct StateBackwardDev {
+  const int32_t* subSize; // [J] by DFS position
+  const int32_t* loadedPos; // [J] every position, ascending
+  const int32_t* jointPos; // [J] DFS position of a joint
+  const int32_t* colStart; // [P + 1]
+  const ColumnSourceDev* colSources; // every entry of the parameter transform, by parameter, in row order
+};
+size_t stateBackwardLdsBytes(int J, int P);
+hipError_t launchStateBackward(
+    const RigDev& rig, const StateBackwardDev& sb, int B, const float* theta, const float* stateGrad, float* thetaGrad, hipStream_t stream);
 int fusedBlocksFor(int n); // number of 16-wide blocks the fused kernel is instantiated for, or -1
 hipError_t launchFusedSolve(
     const RigDev& rig,

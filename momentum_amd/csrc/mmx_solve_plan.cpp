@@ -178,6 +178,13 @@ const char* gradientRefusal(const SolveFacts& f) {
   return nullptr;
 }
 
+const char* stateBackwardRefusal(size_t ldsBytes) {
+  if (ldsBytes > kPlanLdsBudget - 64) {
+    return "mmx_eval_skeleton_state_backward: the rig's tables do not fit the kernel's LDS budget (160 KB)";
+  }
+  return nullptr;
+}
+
 SolvePlan planSolveF64(const SolveFacts& f, const mmx_gn_options& o) {
   if (const char* why = optionsRefusal(o, true)) {
     return refuse(MMX_ERR_INVALID_ARGUMENT, why);

@@ -69,6 +69,9 @@ const char* optionsRefusal(const mmx_gn_options& o, bool checkStepRule);
 const char* waveRefusal(const SolveFacts& f, const mmx_gn_options& o, bool frames);
 // mmx_eval_gradient's scope (include/mmx.h), in its documented order: null when the matrix-free kernel takes the problem
 const char* gradientRefusal(const SolveFacts& f);
+// mmx_eval_skeleton_state_backward's one scope rule: its kernel's LDS bytes for the rig (stateBackwardLdsBytes(J, P),
+// mmx_kernels.hpp) against the workgroup's budget.  Null: the kernel takes the rig.
+const char* stateBackwardRefusal(size_t ldsBytes);
 
 SolvePlan planSolve(const SolveFacts& f, const mmx_gn_options& o); // mmx_solve, mmx_solve_with_history, ..._with_step_history
 SolvePlan planSolveF64(const SolveFacts& f, const mmx_gn_options& o); // mmx_solve_f64
