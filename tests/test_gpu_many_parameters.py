@@ -7,28 +7,11 @@ import pytest
 
 from momentum_amd import capi, make_rig300
 from momentum_amd._abi import GnOptions
-from momentum_amd.rigs import RX, RZ, _build_rig
+from momentum_amd.rigs import _build_rig
+from tests.explicit_route_forms import many_parameter_rig as _many_parameter_rig  # (shared with the explicit-route form tests)
 from tests.helpers import make_problem
 
 pytestmark = pytest.mark.gpu
-
-
-def _many_parameter_rig(extra_dofs, unit=0.01):
-    """make_rig300 (BASELINE configs[4]) with `extra_dofs` rotation parameters on every joint beyond the 72-joint body
-    instead of one on 172 of them: 128 + 228 * extra_dofs parameters."""
-    base = make_rig300(unit=unit)  # (metres: lambda = 0.05 stays above the factor's damping floor, kFactorDamping x the mean diagonal)
-    J0, J = 72, base.num_joints
-    trip = []
-    for r in range(7 * J0):
-        for k in range(base.pt_outer[r], base.pt_outer[r + 1]):
-            trip.append((r, int(base.pt_inner[k]), float(base.pt_value[k])))
-    names = list(base.param_names[:128])
-    assert max(c for _, c, _ in trip) == 127
-    for j in range(J0, J):
-        for d in [RX, RX + 1, RZ, 0, 1, 2, 6][:extra_dofs]:  # rotations first, then translations, then the scale
-            trip.append((j * 7 + d, len(names), 1.0))
-            names.append(f"{base.joint_names[j]}_d{d}")
-    return _build_rig(base.parent, base.pre_rotation, base.translation_offset, trip, len(names), list(base.joint_names), names)
 
 
 def _upload(torch, pb, cons, B):
