@@ -923,6 +923,102 @@ int32_t mmx_eval_skeleton_state_backward_host(
     float* theta_grad_host);
 
 /*
+ * Linear-blend skinning: skeleton state -> posed mesh vertices, and its backward pass.  The counterpart of _forward_kernel /
+ * _backward_kernel in pymomentum/backend/triton_skinning.py (Character.skin_points) and of momentum's applySSD.  Added
+ * without an ABI bump (no struct grows): a library that predates the functions lacks the symbols -- that is the feature probe.
+ *
+ * The skin (mmx_skin_desc) is static per character and shared by the batch; it mirrors momentum's SkinWeights and
+ * Character::inverseBindPose.  joint / weight [V][K] with K <= MMX_MAX_SKIN_INFLUENCES; padding slots carry weight 0 and any
+ * VALID joint index; weights are used as given (no renormalisation).  inverse_bind [J][12] is a 3 x 4 row-major affine
+ * [A_j | a_j] per joint (the convention of mmx_joint_constraint_block::projection and mmx_ellipsoid_limit), NULL = identity.
+ *   meaning     with (t_j, q_j, s_j) the row [b][j] of state [B][J][8] = (tx,ty,tz, qx,qy,qz,qw, s), r_v the rest position of
+ *               vertex v (the skin's, or rest_dev [b][v] when that is not NULL: blend-shaped or identity-dependent meshes,
+ *               the rest_vertices argument of skin_points) and p_vk = A_j r_v + a_j for j = joint[v][k]:
+ *                 out [B][V][3]         out[b][v] = sum_k weight[v][k] ( t_j + s_j qrot(q_j, p_vk) )
+ *                 state_grad [B][J][8]  dL/dstate for out_grad = dL/dout [B][V][3], in the layout of the state
+ *                 rest_grad [B][V][3]   dL/dr[b][v] = sum_k weight[v][k] A_j^T ( s_j R(q_j)^T out_grad[b][v] ); optional
+ *               qrot(q, p) = p + 2 w (u x p) + 2 u x (u x p) with q = (u, w).  The state may come from
+ *               mmx_eval_skeleton_state or from anywhere else: the entry points take the state, not theta or a problem.
+ *   quaternion  used exactly as the state holds it, not renormalised; state_grad is the exact derivative of the polynomial
+ *               above, with no renormalisation term (what mmx_eval_skeleton_state_backward expects of its cotangent).
+ *               Per joint everything follows from twelve sums over the joint's influences, F = sum w g and N = sum w g p^T:
+ *               g_t = F, g_s = <R(q), N>, g_q = s d<R(q), N>/dq.
+ *   written     every entry of out / state_grad / rest_grad.  A zero-weight slot contributes nothing, even when its joint's
+ *               state is not finite; a joint without a non-zero-weight influence gets eight exact zeros in state_grad.
+ *   refusals    before any output is touched: MMX_ERR_INVALID_ARGUMENT for a null required pointer, batch < 1, V < 1, K
+ *               outside 1 .. 8, a joint index outside [0, J) in any slot (zero-weight ones included), a non-finite weight,
+ *               inverse-bind entry or rest position at create; MMX_ERR_UNSUPPORTED at create, with a message that names the
+ *               condition, for a rig whose posed affines (48 bytes per joint) exceed the kernels' LDS budget (160 KB:
+ *               beyond 3412 joints).
+ *   determinism a row of a result depends on that instance's inputs only -- not on the batch size, the instance's position
+ *               in the batch, or the run.  The backward pass is a vertex-to-joint reduction without atomics: each joint's
+ *               sums are taken by one wavefront over the joint's entries of the joint-sorted influence list
+ *               (mmx_host_skin_tables) in a fixed order, lane = entry mod 64 and then a fixed cross-lane tree.
+ * Streams and graphs: mmx_skin_points enqueues one kernel on `stream`, mmx_skin_points_backward one (two with rest_grad_dev)
+ * and returns: no memset node, no stream wait, no host read, no device scratch; the tables are uploaded by mmx_skin_create.
+ * The first call of a process raises a kernel attribute where a rig needs more than 64 KB of LDS: that call is the warm-up,
+ * after it the calls can be captured into a HIP graph like the other entry points.  The _host forms take host arrays
+ * (rest_host NULL or [B][V][3], rest_grad_host NULL to skip), copy in, run, copy out and synchronise like the other host
+ * wrappers.  The handle keeps a reference to its rig, which must outlive it.
+ *
+ * mmx_host_skin_tables is the bookkeeping of the backward pass as a pure host function (no device): the joint-sorted
+ * influence list, every (vertex, slot) pair with a non-zero weight sorted by (joint, vertex, slot), joint_start [J + 1] its
+ * index.  entry_vertex / entry_slot hold up to V * K entries; any output may be NULL.  Only joint, weight and the two sizes
+ * of the descriptor are read.  The backward kernel reads this list and nothing else to decide its summation order.
+ *
+ * PROVENANCE: this restates momentum's applySSD (SkinWeights, Character::inverseBindPose), pymomentum's
+ * Character.skin_points and pymomentum/backend/triton_skinning.py from memory of the reference, without a checkout at hand, so
+ * it carries no file:line citations yet.  To confirm against the reference: kMaxSkinJoints = 8; that weights are not
+ * renormalised at skinning time; the transform order T_world * T_invbind.
+ */
+#define MMX_MAX_SKIN_INFLUENCES 8
+typedef struct mmx_skin_desc {
+  int32_t num_vertices;         /* V >= 1 */
+  int32_t max_influences;       /* K, 1..MMX_MAX_SKIN_INFLUENCES (8) */
+  const int32_t* joint;         /* [V][K] HOST */
+  const float* weight;          /* [V][K] HOST */
+  const float* inverse_bind;    /* [J][12] HOST, NULL = identity */
+  const float* rest_positions;  /* [V][3] HOST */
+} mmx_skin_desc;
+typedef struct mmx_skin mmx_skin;
+
+int32_t mmx_skin_create(mmx_rig* rig, const mmx_skin_desc* desc, mmx_skin** out);
+void mmx_skin_destroy(mmx_skin* skin);
+int32_t mmx_skin_num_vertices(const mmx_skin* skin);
+int32_t mmx_skin_points(
+    mmx_skin* skin,
+    int32_t batch,
+    const float* state_dev,
+    const float* rest_dev /* NULL or [B][V][3] */,
+    float* out_dev,
+    void* stream);
+int32_t mmx_skin_points_backward(
+    mmx_skin* skin,
+    int32_t batch,
+    const float* state_dev,
+    const float* rest_dev,
+    const float* out_grad_dev,
+    float* state_grad_dev,
+    float* rest_grad_dev /* NULL to skip */,
+    void* stream);
+int32_t mmx_skin_points_host(mmx_skin* skin, int32_t batch, const float* state_host, const float* rest_host, float* out_host);
+int32_t mmx_skin_points_backward_host(
+    mmx_skin* skin,
+    int32_t batch,
+    const float* state_host,
+    const float* rest_host,
+    const float* out_grad_host,
+    float* state_grad_host,
+    float* rest_grad_host);
+int32_t mmx_host_skin_tables(
+    int32_t num_joints,
+    const mmx_skin_desc* desc,
+    int32_t* joint_start /* [J+1] */,
+    int32_t* entry_vertex,
+    int32_t* entry_slot,
+    int32_t* num_entries);
+
+/*
  * Numerical diagnostics of the LAST single-precision solve on this handle (one-launch and wide routes;
  * MMX_ERR_UNSUPPORTED after a solve on the explicit-Jacobian route or before the first solve): diag_dev [B][4] floats
  *   [0] the precision estimate MMX_SOLVE_PRECISION_SUSPECT is decided on (relative to |theta|)

@@ -831,6 +831,90 @@ class BatchedSkeletonState {
   std::vector<SkeletonState> states_;
 };
 
+// Linear-blend skinning on a device character (mmx_skin): momentum's SkinWeights (index / weight [V][K], K <= 8),
+// Character::inverseBindPose as 3 x 4 row-major affines [J][12] (empty = identity) and the mesh's rest vertices [V][3].
+// skinPoints: skeleton state [batch][numJoints][8] = (tx,ty,tz, qx,qy,qz,qw, s) -> posed vertices [batch][V][3] (applySSD for
+// every batch element); skinPointsBackward: its vector-Jacobian product.  restPositions: empty (the skin's own) or per-element
+// rest vertices [batch][V][3].  The host forms copy in, run, copy out and synchronise; the device forms take device pointers
+// and a hipStream_t (as void*) and only enqueue kernels.  The skin shares the character's rig handle and keeps it alive.
+class DeviceSkin {
+ public:
+  struct Gradients {
+    std::vector<float> state; // [batch][numJoints][8]
+    std::vector<float> restPositions; // [batch][V][3], empty unless asked for
+  };
+  DeviceSkin(
+      const DeviceCharacter& character, size_t maxInfluences, const std::vector<int32_t>& joint, const std::vector<float>& weight,
+      const std::vector<float>& inverseBind, const std::vector<float>& restPositions)
+      : character_(character), numVertices_(restPositions.size() / 3) {
+    if (maxInfluences == 0 || restPositions.size() % 3 != 0 || joint.size() != numVertices_ * maxInfluences || weight.size() != joint.size()) {
+      throw std::runtime_error("momentum_amd: skin arrays must be [V][K] (joint, weight) and [V][3] (rest positions)");
+    }
+    if (!inverseBind.empty() && inverseBind.size() != character.numJoints() * 12) {
+      throw std::runtime_error("momentum_amd: inverseBind.size() != numJoints * 12");
+    }
+    mmx_skin_desc d{};
+    d.num_vertices = int32_t(numVertices_);
+    d.max_influences = int32_t(maxInfluences);
+    d.joint = joint.data();
+    d.weight = weight.data();
+    d.inverse_bind = inverseBind.empty() ? nullptr : inverseBind.data();
+    d.rest_positions = restPositions.data();
+    mmx_skin* h = nullptr;
+    check(mmx_skin_create(character.handle(), &d, &h));
+    handle_.reset(h, [](mmx_skin* p) { mmx_skin_destroy(p); });
+  }
+  mmx_skin* handle() const {
+    return handle_.get();
+  }
+  size_t numVertices() const {
+    return numVertices_;
+  }
+  std::vector<float> skinPoints(size_t batch, const std::vector<float>& state, const std::vector<float>& restPositions = {}) const {
+    checkSizes(batch, state, restPositions);
+    std::vector<float> out(batch * numVertices_ * 3);
+    check(mmx_skin_points_host(handle_.get(), int32_t(batch), state.data(), restPositions.empty() ? nullptr : restPositions.data(), out.data()));
+    return out;
+  }
+  Gradients skinPointsBackward(
+      size_t batch, const std::vector<float>& state, const std::vector<float>& vertexGradient, const std::vector<float>& restPositions = {},
+      bool wantRestGradient = false) const {
+    checkSizes(batch, state, restPositions);
+    if (vertexGradient.size() != batch * numVertices_ * 3) {
+      throw std::runtime_error("momentum_amd: vertexGradient.size() != batch * numVertices * 3");
+    }
+    Gradients g;
+    g.state.resize(state.size());
+    g.restPositions.resize(wantRestGradient ? vertexGradient.size() : 0);
+    check(mmx_skin_points_backward_host(
+        handle_.get(), int32_t(batch), state.data(), restPositions.empty() ? nullptr : restPositions.data(), vertexGradient.data(), g.state.data(),
+        wantRestGradient ? g.restPositions.data() : nullptr));
+    return g;
+  }
+  // device forms: every pointer is device memory of the character's device; restPositions / restGradient may be null
+  void skinPoints(size_t batch, const float* state, const float* restPositions, float* out, void* stream) const {
+    check(mmx_skin_points(handle_.get(), int32_t(batch), state, restPositions, out, stream));
+  }
+  void skinPointsBackward(
+      size_t batch, const float* state, const float* restPositions, const float* vertexGradient, float* stateGradient, float* restGradient,
+      void* stream) const {
+    check(mmx_skin_points_backward(handle_.get(), int32_t(batch), state, restPositions, vertexGradient, stateGradient, restGradient, stream));
+  }
+
+ private:
+  void checkSizes(size_t batch, const std::vector<float>& state, const std::vector<float>& restPositions) const {
+    if (batch == 0 || state.size() != batch * character_.numJoints() * 8) {
+      throw std::runtime_error("momentum_amd: state.size() != batch * numJoints * 8");
+    }
+    if (!restPositions.empty() && restPositions.size() != batch * numVertices_ * 3) {
+      throw std::runtime_error("momentum_amd: restPositions.size() != batch * numVertices * 3");
+    }
+  }
+  DeviceCharacter character_; // (shares the rig handle: keeps it alive)
+  std::shared_ptr<mmx_skin> handle_;
+  size_t numVertices_ = 0;
+};
+
 class BatchedGaussNewtonSolver {
  public:
   BatchedGaussNewtonSolver(const SolverOptions& options, BatchedSkeletonSolverFunction* function) : fn_(function) {

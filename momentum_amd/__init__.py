@@ -12,6 +12,7 @@ from .rigs import (  # noqa: F401
     make_humanoid72,
     make_rig300,
     humanoid72_landmark_joints,
+    make_test_skin,
 )
 
-__all__ = ["Rig", "make_test_character", "make_humanoid72", "make_rig300", "humanoid72_landmark_joints"]
+__all__ = ["Rig", "make_test_character", "make_humanoid72", "make_rig300", "humanoid72_landmark_joints", "make_test_skin"]

@@ -42,6 +42,20 @@ class RigDesc(C.Structure):
     ]
 
 
+class SkinDesc(C.Structure):
+    """mmx_skin_desc: the skin of linear-blend skinning (host arrays)."""
+
+    _fields_ = [
+        ("num_vertices", C.c_int32),
+        ("max_influences", C.c_int32),
+        ("joint", c_int32_p),
+        ("weight", c_float_p),
+        ("inverse_bind", c_float_p),
+        ("rest_positions", c_float_p),
+    ]
+
+
+MMX_MAX_SKIN_INFLUENCES = 8
 MMX_LOSS_WELSCH = float(np.finfo(np.float32).min)  # GeneralizedLossT::kWelsch
 MMX_LIMIT_MINMAX = 0  # momentum::LimitType values (character/parameter_limits.h:20-31)
 MMX_LIMIT_MINMAX_JOINT = 1

@@ -1,6 +1,8 @@
 """torch.autograd bindings of the batched kernels: skeleton_state(problem, theta) is Problem.skeleton_state with a backward
 pass (mmx_eval_skeleton_state_backward), the counterpart of pymomentum/backend/triton_fk.py's _forward_kernel /
-_backward_kernel pair.  Both directions are one kernel on the current stream; nothing goes through the host."""
+_backward_kernel pair; skin_points(skin, state) is Skin.skin_points with Skin.skin_points_backward, the counterpart of
+triton_skinning.py's pair.  Each direction of each stage is one kernel on the current stream (the rest gradient, when asked
+for, one more); nothing goes through the host.  The two compose: skin_points(skin, skeleton_state(problem, theta))."""
 from __future__ import annotations
 
 import torch
@@ -26,3 +28,29 @@ def skeleton_state(problem, theta):
     if not (theta.requires_grad and torch.is_grad_enabled()):
         return problem.skeleton_state(theta)
     return _SkeletonState.apply(theta, problem)
+
+
+class _SkinPoints(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, rest, skin):
+        ctx.skin = skin
+        ctx.save_for_backward(state, rest if rest is not None else state.new_empty(0))
+        ctx.has_rest = rest is not None
+        return skin.skin_points(state, rest)
+
+    @staticmethod
+    def backward(ctx, grad):
+        state, rest = ctx.saved_tensors
+        want_rest = ctx.has_rest and ctx.needs_input_grad[1]
+        state_grad, rest_grad = ctx.skin.skin_points_backward(state, grad.contiguous(), rest if ctx.has_rest else None, want_rest_grad=want_rest)
+        return (state_grad if ctx.needs_input_grad[0] else None), rest_grad, None
+
+
+def skin_points(skin, state, rest=None):
+    """Posed vertices [B,V,3] of state [B,J,8] (float32, cuda, contiguous) on `skin` (capi.Skin), differentiable with respect
+    to the state and to per-instance rest positions rest [B,V,3] when that is a tensor requiring grad.  Without an input that
+    requires grad (or under torch.no_grad()) this is skin.skin_points(state, rest): no graph node, no extra work."""
+    needs = state.requires_grad or (rest is not None and rest.requires_grad)
+    if not (needs and torch.is_grad_enabled()):
+        return skin.skin_points(state, rest)
+    return _SkinPoints.apply(state.contiguous(), rest, skin)

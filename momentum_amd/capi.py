@@ -32,6 +32,8 @@ SYMBOLS = [
     "mmx_solve_frames", "mmx_solve_frames_host",
     "mmx_eval_gradient", "mmx_eval_gradient_host",
     "mmx_eval_skeleton_state_backward", "mmx_eval_skeleton_state_backward_host",
+    "mmx_skin_create", "mmx_skin_destroy", "mmx_skin_num_vertices", "mmx_skin_points", "mmx_skin_points_backward",
+    "mmx_skin_points_host", "mmx_skin_points_backward_host", "mmx_host_skin_tables",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
     "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
@@ -100,6 +102,15 @@ def lib() -> C.CDLL:
     L.mmx_eval_gradient_host.argtypes = [vp, vp, vp, vp]
     L.mmx_eval_skeleton_state_backward.argtypes = [vp, vp, vp, vp, vp]
     L.mmx_eval_skeleton_state_backward_host.argtypes = [vp, vp, vp, vp]
+    L.mmx_skin_create.argtypes = [vp, C.POINTER(_abi.SkinDesc), C.POINTER(vp)]
+    L.mmx_skin_destroy.argtypes = [vp]
+    L.mmx_skin_destroy.restype = None
+    L.mmx_skin_num_vertices.argtypes = [vp]
+    L.mmx_skin_points.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.mmx_skin_points_backward.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.mmx_skin_points_host.argtypes = [vp, i32, vp, vp, vp]
+    L.mmx_skin_points_backward_host.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.mmx_host_skin_tables.argtypes = [i32, C.POINTER(_abi.SkinDesc), _abi.c_int32_p, _abi.c_int32_p, _abi.c_int32_p, _abi.c_int32_p]
     L.mmx_eval_jacobian_host.argtypes = [vp, vp, vp, vp, vp, i32]
     L.mmx_eval_skeleton_state_host.argtypes = [vp, vp, vp]
     L.mmx_debug_tree_normal_equations.argtypes = [vp, vp, vp, vp, vp]
@@ -230,6 +241,32 @@ def host_f64_assembly_list(rig: Rig, solve_list, pos_parent, ori_parent, units_p
     return chunks
 
 
+def _skin_desc(joint, weight, inverse_bind=None, rest=None):
+    """mmx_skin_desc over C-contiguous copies of the arrays: (descriptor, the arrays it points into -- keep them alive)."""
+    jt = np.ascontiguousarray(joint, dtype=np.int32)
+    wt = np.ascontiguousarray(weight, dtype=np.float32)
+    assert jt.ndim == 2 and jt.shape == wt.shape, (jt.shape, wt.shape)
+    ib = None if inverse_bind is None else np.ascontiguousarray(inverse_bind, dtype=np.float32).reshape(-1, 12)
+    rs = None if rest is None else np.ascontiguousarray(rest, dtype=np.float32)
+    assert rs is None or rs.shape == (jt.shape[0], 3), rs.shape
+    d = _abi.SkinDesc(
+        jt.shape[0], jt.shape[1], as_ptr(jt, C.c_int32), as_ptr(wt, C.c_float),
+        _abi.c_float_p() if ib is None else as_ptr(ib, C.c_float), _abi.c_float_p() if rs is None else as_ptr(rs, C.c_float),
+    )  # fmt: skip
+    return d, (jt, wt, ib, rs)
+
+
+def host_skin_tables(num_joints: int, joint, weight) -> dict:
+    """The joint-sorted influence list of the skinning backward pass (mmx_host_skin_tables, no GPU needed): every (vertex,
+    slot) pair with a non-zero weight sorted by (joint, vertex, slot): dict(joint_start [J+1], entry_vertex, entry_slot)."""
+    d, keep = _skin_desc(joint, weight)
+    start = np.zeros(int(num_joints) + 1, np.int32)
+    ev, es = (np.zeros(max(keep[0].size, 1), np.int32) for _ in range(2))
+    n = C.c_int32(0)
+    _check(lib().mmx_host_skin_tables(int(num_joints), C.byref(d), as_ptr(start, C.c_int32), as_ptr(ev, C.c_int32), as_ptr(es, C.c_int32), C.byref(n)))
+    return dict(joint_start=start, entry_vertex=ev[: n.value].copy(), entry_slot=es[: n.value].copy())
+
+
 def _stream_ptr() -> C.c_void_p:
     import torch
 
@@ -260,6 +297,83 @@ class RigHandle:
             self.close()
         except Exception:
             pass
+
+
+class Skin:
+    """A skin on a rig (mmx_skin): linear-blend skinning, skeleton state [B,J,8] -> posed vertices [B,V,3], and its backward
+    pass.  joint / weight [V,K] (K <= 8; padding slots: weight 0 and a valid joint), inverse_bind [J,12] (3 x 4 row-major
+    affines, None = identity), rest [V,3].  The counterpart of pymomentum's Character.skin_points / triton_skinning.py."""
+
+    def __init__(self, rig_handle: "RigHandle", joint, weight, inverse_bind=None, rest=None):
+        import torch
+
+        self.rh = rig_handle
+        self.J = rig_handle.rig.num_joints
+        d, keep = _skin_desc(joint, weight, inverse_bind, rest)
+        assert keep[2] is None or keep[2].shape == (self.J, 12), keep[2].shape
+        self.V, self.K = keep[0].shape
+        self.device = torch.device("cuda", rig_handle.device)
+        self._h = C.c_void_p(0)
+        _check(lib().mmx_skin_create(rig_handle._h, C.byref(d), C.byref(self._h)))
+
+    def close(self) -> None:
+        if self._h:
+            lib().mmx_skin_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _f32(self, t, shape, what):
+        import torch
+
+        assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), what
+        assert tuple(t.shape) == shape, (what, tuple(t.shape), shape)
+        return t
+
+    def _batch(self, state) -> int:
+        import torch
+
+        assert isinstance(state, torch.Tensor) and state.dim() == 3 and state.shape[0] >= 1, "state must be [B,J,8]"
+        B = int(state.shape[0])
+        self._f32(state, (B, self.J, 8), "state")
+        return B
+
+    def skin_points(self, state, rest=None, out=None):
+        """Posed vertices [B,V,3] float32 of state [B,J,8] (float32, cuda, contiguous); rest: None (the skin's rest positions) or
+        per-instance rest positions [B,V,3].  One kernel on the current stream."""
+        import torch
+
+        B = self._batch(state)
+        if rest is not None:
+            self._f32(rest, (B, self.V, 3), "rest")
+        if out is None:
+            out = torch.empty((B, self.V, 3), dtype=torch.float32, device=self.device)
+        self._f32(out, (B, self.V, 3), "out")
+        _check(lib().mmx_skin_points(self._h, B, _dev(state), _dev(rest), _dev(out), _stream_ptr()))
+        return out
+
+    def skin_points_backward(self, state, grad_out, rest=None, want_rest_grad=False, state_grad=None, rest_grad=None):
+        """(dL/dstate [B,J,8], dL/drest [B,V,3] or None) for grad_out = dL/dvertices [B,V,3]: a vertex-to-joint reduction in a
+        fixed order, without atomics.  Every entry is written; a joint without influence gets exact zeros."""
+        import torch
+
+        B = self._batch(state)
+        self._f32(grad_out, (B, self.V, 3), "grad_out")
+        if rest is not None:
+            self._f32(rest, (B, self.V, 3), "rest")
+        if state_grad is None:
+            state_grad = torch.empty((B, self.J, 8), dtype=torch.float32, device=self.device)
+        self._f32(state_grad, (B, self.J, 8), "state_grad")
+        if want_rest_grad and rest_grad is None:
+            rest_grad = torch.empty((B, self.V, 3), dtype=torch.float32, device=self.device)
+        if rest_grad is not None:
+            self._f32(rest_grad, (B, self.V, 3), "rest_grad")
+        _check(lib().mmx_skin_points_backward(self._h, B, _dev(state), _dev(rest), _dev(grad_out), _dev(state_grad), _dev(rest_grad), _stream_ptr()))
+        return state_grad, rest_grad
 
 
 # Route every Problem created from here on starts with ("auto" | "fused" | "wide" | "explicit_jacobian" | "wave"): the parity tests

@@ -25,6 +25,7 @@
 #include "mmx_constraint_intake.hpp"
 #include "mmx_host_tables.hpp"
 #include "mmx_kernels.hpp"
+#include "mmx_skin_tables.hpp"
 #include "mmx_solve_plan.hpp"
 
 namespace {
@@ -229,6 +230,14 @@ struct mmx_rig {
     d.pt_offsets = ptOffsets.data();
     return d;
   }
+};
+
+// A skin on a rig (mmx_skin_create): the uploaded tables of linear-blend skinning and the staging buffers of the _host forms
+struct mmx_skin {
+  mmx_rig* rig = nullptr;
+  DevBuf dJoint, dWeight, dInverseBind, dRest, dJointStart, dEntryVertex, dEntryWeight, dWaveStart;
+  mmx::SkinDev dev{};
+  DevBuf sState, sRest, sOut, sStateGrad, sRestGrad;
 };
 
 struct mmx_problem {
@@ -2529,6 +2538,195 @@ int32_t mmx_eval_jacobian_host(
   }
   if (err_host) {
     MMX_HIP(hipMemcpy(err_host, pb->sErr.p, B * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return MMX_OK;
+}
+
+// ---- linear-blend skinning (mmx_skinning.hip; bookkeeping: mmx_skin_tables.cpp)
+int32_t mmx_host_skin_tables(
+    int32_t num_joints, const mmx_skin_desc* desc, int32_t* joint_start, int32_t* entry_vertex, int32_t* entry_slot, int32_t* num_entries) {
+  std::string err;
+  const int32_t rc = mmx::validateSkinDesc(num_joints, desc, false, err);
+  if (rc != MMX_OK) {
+    return fail(rc, "mmx_host_skin_tables: " + err);
+  }
+  const mmx::SkinTables t = mmx::buildSkinTables(num_joints, desc);
+  if (joint_start) {
+    std::memcpy(joint_start, t.jointStart.data(), sizeof(int32_t) * t.jointStart.size());
+  }
+  if (entry_vertex && !t.entryVertex.empty()) {
+    std::memcpy(entry_vertex, t.entryVertex.data(), sizeof(int32_t) * t.entryVertex.size());
+  }
+  if (entry_slot && !t.entrySlot.empty()) {
+    std::memcpy(entry_slot, t.entrySlot.data(), sizeof(int32_t) * t.entrySlot.size());
+  }
+  if (num_entries) {
+    *num_entries = int32_t(t.entryVertex.size());
+  }
+  return MMX_OK;
+}
+
+int32_t mmx_skin_create(mmx_rig* rig, const mmx_skin_desc* desc, mmx_skin** out) {
+  MMX_ZONE("mmx_skin_create");
+  if (out == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_create: out is null");
+  }
+  *out = nullptr;
+  if (rig == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_create: rig handle is null");
+  }
+  std::string err;
+  const int32_t rc = mmx::validateSkinDesc(rig->J, desc, true, err);
+  if (rc != MMX_OK) {
+    return fail(rc, "mmx_skin_create: " + err);
+  }
+  if (const char* why = mmx::skinRefusal(rig->J)) {
+    return fail(MMX_ERR_UNSUPPORTED, why);
+  }
+  std::unique_ptr<mmx_skin> sk(new (std::nothrow) mmx_skin());
+  if (!sk) {
+    return fail(MMX_ERR_OUT_OF_MEMORY, "host allocation failed");
+  }
+  sk->rig = rig;
+  const size_t V = size_t(desc->num_vertices), K = size_t(desc->max_influences), J = size_t(rig->J);
+  const mmx::SkinTables t = mmx::buildSkinTables(rig->J, desc);
+  std::vector<float> ib(J * 12, 0.f);
+  for (size_t j = 0; j < J; ++j) {
+    if (desc->inverse_bind != nullptr) {
+      std::copy(desc->inverse_bind + 12 * j, desc->inverse_bind + 12 * j + 12, ib.begin() + 12 * j);
+    } else {
+      ib[12 * j] = ib[12 * j + 5] = ib[12 * j + 10] = 1.f;
+    }
+  }
+  MMX_HIP(hipSetDevice(rig->device));
+  MMX_HIP(upload(sk->dJoint, std::vector<int32_t>(desc->joint, desc->joint + V * K)));
+  MMX_HIP(upload(sk->dWeight, std::vector<float>(desc->weight, desc->weight + V * K)));
+  MMX_HIP(upload(sk->dInverseBind, ib));
+  MMX_HIP(upload(sk->dRest, std::vector<float>(desc->rest_positions, desc->rest_positions + V * 3)));
+  MMX_HIP(upload(sk->dJointStart, t.jointStart));
+  MMX_HIP(upload(sk->dEntryVertex, t.entryVertex));
+  MMX_HIP(upload(sk->dEntryWeight, t.entryWeight));
+  MMX_HIP(upload(sk->dWaveStart, t.waveStart));
+  mmx::SkinDev& d = sk->dev;
+  d.V = desc->num_vertices, d.K = desc->max_influences, d.J = rig->J, d.numWaves = int32_t(t.waveStart.size()) - 1;
+  d.joint = sk->dJoint.as<int32_t>(), d.weight = sk->dWeight.as<float>();
+  d.inverseBind = sk->dInverseBind.as<float>(), d.rest = sk->dRest.as<float>();
+  d.jointStart = sk->dJointStart.as<int32_t>(), d.entryVertex = sk->dEntryVertex.as<int32_t>();
+  d.entryWeight = sk->dEntryWeight.as<float>(), d.waveStart = sk->dWaveStart.as<int32_t>();
+  *out = sk.release();
+  return MMX_OK;
+}
+
+void mmx_skin_destroy(mmx_skin* skin) {
+  if (skin != nullptr) {
+    if (skin->rig != nullptr) {
+      (void)hipSetDevice(skin->rig->device);
+    }
+    delete skin;
+  }
+}
+
+int32_t mmx_skin_num_vertices(const mmx_skin* skin) {
+  return skin ? skin->dev.V : 0;
+}
+
+int32_t mmx_skin_points(mmx_skin* skin, int32_t batch, const float* state_dev, const float* rest_dev, float* out_dev, void* stream) {
+  MMX_ZONE("mmx_skin_points (linear-blend skinning)");
+  if (skin == nullptr || state_dev == nullptr || out_dev == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_points: skin / state / out is null");
+  }
+  if (batch < 1) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_points: batch must be >= 1");
+  }
+  MMX_HIP(hipSetDevice(skin->rig->device));
+  MMX_HIP(mmx::launchSkinPoints(skin->dev, batch, state_dev, rest_dev, out_dev, static_cast<hipStream_t>(stream)));
+  return MMX_OK;
+}
+
+int32_t mmx_skin_points_backward(
+    mmx_skin* skin,
+    int32_t batch,
+    const float* state_dev,
+    const float* rest_dev,
+    const float* out_grad_dev,
+    float* state_grad_dev,
+    float* rest_grad_dev,
+    void* stream) {
+  MMX_ZONE("mmx_skin_points_backward (linear-blend skinning VJP)");
+  if (skin == nullptr || state_dev == nullptr || out_grad_dev == nullptr || state_grad_dev == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_points_backward: skin / state / out_grad / state_grad is null");
+  }
+  if (batch < 1) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_points_backward: batch must be >= 1");
+  }
+  MMX_HIP(hipSetDevice(skin->rig->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  MMX_HIP(mmx::launchSkinPointsBackward(skin->dev, batch, state_dev, rest_dev, out_grad_dev, state_grad_dev, s));
+  if (rest_grad_dev != nullptr) {
+    MMX_HIP(mmx::launchSkinRestGrad(skin->dev, batch, state_dev, out_grad_dev, rest_grad_dev, s));
+  }
+  return MMX_OK;
+}
+
+int32_t mmx_skin_points_host(mmx_skin* skin, int32_t batch, const float* state_host, const float* rest_host, float* out_host) {
+  MMX_ZONE("mmx_skin_points_host");
+  if (skin == nullptr || state_host == nullptr || out_host == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_points_host: skin / state / out is null");
+  }
+  if (batch < 1) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_points_host: batch must be >= 1");
+  }
+  const size_t nState = size_t(batch) * size_t(skin->dev.J) * 8 * sizeof(float), nVert = size_t(batch) * size_t(skin->dev.V) * 3 * sizeof(float);
+  MMX_HIP(hipSetDevice(skin->rig->device));
+  MMX_HIP(skin->sState.ensure(nState));
+  MMX_HIP(skin->sOut.ensure(nVert));
+  MMX_HIP(hipMemcpy(skin->sState.p, state_host, nState, hipMemcpyHostToDevice));
+  if (rest_host != nullptr) {
+    MMX_HIP(skin->sRest.ensure(nVert));
+    MMX_HIP(hipMemcpy(skin->sRest.p, rest_host, nVert, hipMemcpyHostToDevice));
+  }
+  MMX_TRY(mmx_skin_points(skin, batch, skin->sState.as<float>(), rest_host ? skin->sRest.as<float>() : nullptr, skin->sOut.as<float>(), nullptr));
+  MMX_HIP(hipDeviceSynchronize());
+  MMX_HIP(hipMemcpy(out_host, skin->sOut.p, nVert, hipMemcpyDeviceToHost));
+  return MMX_OK;
+}
+
+int32_t mmx_skin_points_backward_host(
+    mmx_skin* skin,
+    int32_t batch,
+    const float* state_host,
+    const float* rest_host,
+    const float* out_grad_host,
+    float* state_grad_host,
+    float* rest_grad_host) {
+  MMX_ZONE("mmx_skin_points_backward_host");
+  if (skin == nullptr || state_host == nullptr || out_grad_host == nullptr || state_grad_host == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_points_backward_host: skin / state / out_grad / state_grad is null");
+  }
+  if (batch < 1) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_points_backward_host: batch must be >= 1");
+  }
+  const size_t nState = size_t(batch) * size_t(skin->dev.J) * 8 * sizeof(float), nVert = size_t(batch) * size_t(skin->dev.V) * 3 * sizeof(float);
+  MMX_HIP(hipSetDevice(skin->rig->device));
+  MMX_HIP(skin->sState.ensure(nState));
+  MMX_HIP(skin->sOut.ensure(nVert));
+  MMX_HIP(skin->sStateGrad.ensure(nState));
+  MMX_HIP(hipMemcpy(skin->sState.p, state_host, nState, hipMemcpyHostToDevice));
+  MMX_HIP(hipMemcpy(skin->sOut.p, out_grad_host, nVert, hipMemcpyHostToDevice));
+  if (rest_host != nullptr) {
+    MMX_HIP(skin->sRest.ensure(nVert));
+    MMX_HIP(hipMemcpy(skin->sRest.p, rest_host, nVert, hipMemcpyHostToDevice));
+  }
+  if (rest_grad_host != nullptr) {
+    MMX_HIP(skin->sRestGrad.ensure(nVert));
+  }
+  MMX_TRY(mmx_skin_points_backward(
+      skin, batch, skin->sState.as<float>(), rest_host ? skin->sRest.as<float>() : nullptr, skin->sOut.as<float>(), skin->sStateGrad.as<float>(),
+      rest_grad_host ? skin->sRestGrad.as<float>() : nullptr, nullptr));
+  MMX_HIP(hipDeviceSynchronize());
+  MMX_HIP(hipMemcpy(state_grad_host, skin->sStateGrad.p, nState, hipMemcpyDeviceToHost));
+  if (rest_grad_host != nullptr) {
+    MMX_HIP(hipMemcpy(rest_grad_host, skin->sRestGrad.p, nVert, hipMemcpyDeviceToHost));
   }
   return MMX_OK;
 }

@@ -233,6 +233,24 @@ struct StateBackwardDev {
 size_t stateBackwardLdsBytes(int J, int P);
 hipError_t launchStateBackward(
     const RigDev& rig, const StateBackwardDev& sb, int B, const float* theta, const float* stateGrad, float* thetaGrad, hipStream_t stream);
+// Linear-blend skinning (mmx_skinning.hip): the skin's tables on the device (mmx_skin_tables.hpp builds the joint-sorted
+// influence list and the wave partition).  One kernel node per launch function; restInst null = the skin's own rest positions.
+struct SkinDev {
+  int32_t V, K, J, numWaves;
+  const int32_t* joint; // [V][K]
+  const float* weight; // [V][K]
+  const float* inverseBind; // [J][12] row-major [A | a] (identity rows where the caller gave none)
+  const float* rest; // [V][3]
+  const int32_t* jointStart; // [J + 1]
+  const int32_t* entryVertex; // [numEntries] sorted by (joint, vertex, slot)
+  const float* entryWeight; // [numEntries]
+  const int32_t* waveStart; // [numWaves + 1]
+};
+constexpr int kSkinTile = 1024; // vertices of one instance a forward workgroup takes
+hipError_t launchSkinPoints(const SkinDev& sk, int B, const float* state, const float* restInst, float* out, hipStream_t stream);
+hipError_t launchSkinRestGrad(const SkinDev& sk, int B, const float* state, const float* outGrad, float* restGrad, hipStream_t stream);
+hipError_t launchSkinPointsBackward(
+    const SkinDev& sk, int B, const float* state, const float* restInst, const float* outGrad, float* stateGrad, hipStream_t stream);
 int fusedBlocksFor(int n); // number of 16-wide blocks the fused kernel is instantiated for, or -1
 hipError_t launchFusedSolve(
     const RigDev& rig,

@@ -9,8 +9,10 @@ parameter_transform.h:62-95).  Generators:
                            (momentum/test/character/character_helpers.cpp:38-55,106-149)
   make_humanoid72(...)     BASELINE.json configs 2-4 (72-joint humanoid, P=128 or P=219)
   make_rig300(...)         BASELINE.json config 5 (300-joint hand+body rig, P=300)
+  make_test_skin(...)      a synthetic skin (SkinWeights, inverse bind pose, rest vertices) on any of them
 
-No compute lives here (integer/array bookkeeping only).
+No compute lives here (integer/array bookkeeping only; make_test_skin composes the rest pose in float64 numpy to place
+its vertices and invert the bind pose).
 """
 from __future__ import annotations
 
@@ -325,3 +327,88 @@ def make_rig300(seed: int = 12345, unit: float = 1.0) -> Rig:
         pnames.append(f"{names[j]}_r{'xyz'[d - RX]}")
     assert len(pnames) == 300
     return _build_rig(parent, np.stack(pre), np.stack(off), trip, len(pnames), names, pnames)
+
+
+def rest_pose_transforms(rig: Rig) -> np.ndarray:
+    """World transforms of the rest pose (all model parameters zero) as float64 3 x 4 affines [s R | t]: [J, 3, 4].  Array
+    bookkeeping for make_test_skin (momentum/character/joint_state.cpp:22-65: local rotation = pre-rotation * rz * ry * rx)."""
+
+    def qmul(a, b):
+        av, aw, bv, bw = a[:3], a[3], b[:3], b[3]
+        return np.concatenate([aw * bv + bw * av + np.cross(av, bv), [aw * bw - av @ bv]])
+
+    def qmat(q):
+        x, y, z, w = q / np.linalg.norm(q)
+        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                         [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                         [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])  # fmt: skip
+
+    J = rig.num_joints
+    jp = rig.pt_offsets.astype(np.float64).reshape(J, PARAMS_PER_JOINT)
+    out = np.zeros((J, 3, 4))
+    quat, scale = np.zeros((J, 4)), np.ones(J)
+    for j in range(J):
+        q = rig.pre_rotation[j].astype(np.float64)
+        for d, axis in ((RZ, 2), (RY, 1), (RX, 0)):
+            h = np.zeros(4)
+            h[axis], h[3] = np.sin(0.5 * jp[j, d]), np.cos(0.5 * jp[j, d])
+            q = qmul(q, h)
+        t, s = rig.translation_offset[j].astype(np.float64) + jp[j, :3], 2.0 ** jp[j, SC]
+        p = int(rig.parent[j])
+        if p >= 0:
+            t = out[p, :, 3] + out[p, :, :3] @ t
+            q, s = qmul(quat[p], q), scale[p] * s
+        quat[j], scale[j] = q, s
+        out[j, :, :3], out[j, :, 3] = s * qmat(q), t
+    return out
+
+
+@dataclass
+class TestSkin:
+    """A skin for Skin(rig_handle, joint, weight, inverse_bind, rest): what momentum's SkinWeights, Character::inverseBindPose
+    and the mesh's rest vertices carry."""
+
+    __test__ = False  # (not a pytest class)
+    joint: np.ndarray  # [V,K] int32
+    weight: np.ndarray  # [V,K] float32, rows sum to 1; unused slots 0
+    inverse_bind: np.ndarray  # [J,12] float32, 3 x 4 row-major
+    rest: np.ndarray  # [V,3] float32
+
+
+def make_test_skin(rig: Rig, num_vertices: int, max_influences: int, seed: int, random_affine: bool = False) -> TestSkin:
+    """Synthetic skin for tests and scripts/skinning_rate.py: vertices scattered around the rest pose's bones, each bound to its
+    nearest joint and that joint's tree neighbours (parent, then children) with positive weights that sum to 1; unused slots
+    carry weight 0 (and the nearest joint's index).  inverse_bind is the float64 inverse of the rest-pose world transforms;
+    random_affine perturbs every entry of it, so that the full 3 x 4 is exercised."""
+    rng = np.random.default_rng(seed)
+    J, V, K = rig.num_joints, int(num_vertices), int(max_influences)
+    assert V >= 1 and 1 <= K <= 8
+    world = rest_pose_transforms(rig)
+    pos = world[:, :, 3]
+    children: List[List[int]] = [[] for _ in range(J)]
+    for j in range(1, J):
+        if rig.parent[j] >= 0:
+            children[int(rig.parent[j])].append(j)
+    bone = np.array([np.linalg.norm(pos[j] - pos[int(rig.parent[j])]) if rig.parent[j] >= 0 else 0.0 for j in range(J)])
+    spread = 0.25 * (bone[bone > 0].mean() if (bone > 0).any() else 1.0)
+    at = np.sort(rng.integers(0, J, size=V))  # bone by bone: neighbours in the vertex order share joints, as a mesh's do
+    along = rng.uniform(0.0, 1.0, size=V)
+    par = np.where(rig.parent[at] >= 0, rig.parent[at], at)
+    rest = pos[at] + along[:, None] * (pos[par] - pos[at]) + spread * rng.normal(size=(V, 3))
+    joint = np.zeros((V, K), np.int32)
+    weight = np.zeros((V, K), np.float32)
+    for v in range(V):
+        near = int(np.argmin(np.linalg.norm(pos - rest[v], axis=1)))
+        cand = [near] + ([int(rig.parent[near])] if rig.parent[near] >= 0 else []) + children[near]
+        cand = cand[:K]
+        w = 1.0 / (spread + np.linalg.norm(pos[cand] - rest[v], axis=1))
+        w = (w / w.sum()).astype(np.float32)
+        joint[v], joint[v, : len(cand)] = near, cand
+        weight[v, : len(cand)] = w
+    inv = np.zeros((J, 3, 4))
+    for j in range(J):
+        A = np.linalg.inv(world[j, :, :3])
+        inv[j, :, :3], inv[j, :, 3] = A, -A @ world[j, :, 3]
+    if random_affine:
+        inv += 0.1 * rng.normal(size=inv.shape)
+    return TestSkin(joint, weight, inv.reshape(J, 12).astype(np.float32), rest.astype(np.float32))
