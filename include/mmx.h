@@ -1019,6 +1019,90 @@ int32_t mmx_host_skin_tables(
     int32_t* num_entries);
 
 /*
+ * Batched nearest-point queries: for every source point of every instance, the index of the nearest eligible target point
+ * of the same instance (and, optionally, its squared distance and the point itself).  The counterpart of
+ * pymomentum.geometry.find_closest_points and of its overload with normals, which run on the CPU; what an ICP loop does
+ * with the posed vertices of mmx_skin_points in every iteration.  Stateless: no handle, the arrays are the call's only
+ * state, on the current device.  Added without an ABI bump (no struct grows): a library that predates the functions lacks
+ * the symbols -- that is the feature probe.
+ *   distance    for source s and target t, dx = s.x - t.x, dy = s.y - t.y, dz = s.z - t.z taken FIRST, in float32, then
+ *                 d2 = fma(dz, dz, fma(dy, dy, dx * dx))
+ *               -- the same instruction sequence for every pair, whichever lane, wave, tile or remainder handles it, so
+ *               two identical target points compute identical bits.  The expanded form |s|^2 + |t|^2 - 2 s.t is not
+ *               used anywhere (in float32 it picks wrong neighbours as soon as the cloud sits away from the origin).
+ *   eligible    a pair is eligible when d2 is finite, d2 <= max_dist * max_dist (the product taken in float32: +inf stays
+ *               +inf) and, with normals, fma(ns.z, nt.z, fma(ns.y, nt.y, ns.x * nt.x)) >= min_normal_dot.  Normals are
+ *               used as given, not renormalised.  Both normal arrays or neither.
+ *   non-finite  every comparison is ordered, so a NaN anywhere in a pair (a coordinate, a normal) makes the pair
+ *               ineligible; so does an infinite coordinate (d2 is then +inf or NaN).  These are ordinary inputs.
+ *   result      the eligible target with the smallest computed d2; among targets with equal computed d2 the lowest index.
+ *               index [B][N] is -1 where no target is eligible; dist2 (optional) is the winning computed d2, +inf where
+ *               index is -1; points (optional) is a copy of the winning target's three floats, zeros where index is -1.
+ *               Every entry of every non-NULL output is written.
+ *   sharing     target_shared != 0: one target cloud [M][3] (and its normals [M][3]) serves every instance; the result is
+ *               bit-identical to the same cloud replicated per instance.
+ *   refusals    before any output is touched: MMX_ERR_INVALID_ARGUMENT for a null required pointer (source, target, index),
+ *               batch, num_source or num_target below 1, max_dist negative or NaN, exactly one of the two normal arrays,
+ *               min_normal_dot NaN when normals are given, a launch grid beyond 2^31 - 1 workgroups.
+ *   determinism a row of a result depends on that instance's inputs only -- not on the batch size, the instance's position
+ *               in the batch, or the run.  No atomics: a lane scans its targets in ascending order with a strict <, and
+ *               where a tile's targets are divided over waves the partial results are combined in a fixed order by the
+ *               lexicographic minimum of (d2, index).
+ * Streams and graphs: mmx_closest_points enqueues ONE kernel on `stream` and returns: no memset node, no stream wait, no
+ * host read, no device scratch, no kernel attribute to raise (the kernel needs 32 KB of LDS).  It can be captured into a HIP
+ * graph from the first call on.  mmx_closest_points_host takes host arrays, copies in, runs, copies out and synchronises
+ * like the other host wrappers.
+ *
+ * mmx_closest_points_plan is the launch decision as a pure host function (no device), the one the launcher itself calls:
+ * how many sources a workgroup owns, how many targets a staged LDS tile holds, and over how many waves a tile's targets are
+ * divided (1 would mean not divided; the kernel as built always divides a tile over its four waves, which all hold the
+ * same sources).  MMX_ERR_INVALID_ARGUMENT for a size below 1 or a grid beyond 2^31 - 1; any output may be NULL.
+ *
+ * PROVENANCE: this restates pymomentum.geometry.find_closest_points (points_source, points_target, max_dist) ->
+ * (closest_points, index, valid) and its overload with normals from memory of the reference, without a checkout at hand,
+ * so it carries no file:line citations yet.  To confirm against the reference: the name and the default of the normal
+ * threshold (remembered as max_normal_dot, default 0; here min_normal_dot, the dot product's lower bound), whether the
+ * reference compares with >= or >, and whether its max_dist test is <= or <.
+ */
+int32_t mmx_closest_points(
+    int32_t batch,
+    int32_t num_source,
+    int32_t num_target,
+    const float* source_dev /* [B][N][3] */,
+    const float* target_dev /* [B][M][3], or [M][3] when target_shared != 0 */,
+    int32_t target_shared,
+    const float* source_normals_dev /* NULL or [B][N][3] */,
+    const float* target_normals_dev /* NULL or laid out like target_dev; both or neither */,
+    float max_dist /* >= 0, +inf allowed */,
+    float min_normal_dot /* read only with normals */,
+    int32_t* index_dev /* [B][N], -1 = no eligible target */,
+    float* dist2_dev /* NULL or [B][N], +inf where index is -1 */,
+    float* points_dev /* NULL or [B][N][3], zeros where index is -1 */,
+    void* stream);
+int32_t mmx_closest_points_host(
+    int32_t batch,
+    int32_t num_source,
+    int32_t num_target,
+    const float* source_host,
+    const float* target_host,
+    int32_t target_shared,
+    const float* source_normals_host,
+    const float* target_normals_host,
+    float max_dist,
+    float min_normal_dot,
+    int32_t* index_host,
+    float* dist2_host,
+    float* points_host);
+int32_t mmx_closest_points_plan(
+    int32_t batch,
+    int32_t num_source,
+    int32_t num_target,
+    int32_t with_normals,
+    int32_t* sources_per_workgroup,
+    int32_t* target_tile,
+    int32_t* target_ways);
+
+/*
  * Numerical diagnostics of the LAST single-precision solve on this handle (one-launch and wide routes;
  * MMX_ERR_UNSUPPORTED after a solve on the explicit-Jacobian route or before the first solve): diag_dev [B][4] floats
  *   [0] the precision estimate MMX_SOLVE_PRECISION_SUSPECT is decided on (relative to |theta|)

@@ -915,6 +915,52 @@ class DeviceSkin {
   size_t numVertices_ = 0;
 };
 
+// Nearest-point queries (mmx_closest_points; pymomentum.geometry.find_closest_points, which runs on the CPU): for every
+// source point [batch][numSource][3] the nearest eligible target point of the same batch element -- targets
+// [batch][numTarget][3], or [numTarget][3] shared by the batch.  Eligible: a finite squared distance <= maxDist^2 and, with
+// normals (both arrays or neither, laid out like the points, not renormalised), n_s . n_t >= minNormalDot.  Ties go to the
+// lowest index.  The device form takes device pointers of the current device and a hipStream_t (as void*) and enqueues one
+// kernel: index [batch][numSource] is -1 without an eligible target, dist2 (may be null) is +inf there, points (may be
+// null) zeros.  The host form copies in, runs, copies out and synchronises.
+struct ClosestPointsOptions {
+  float maxDist = std::numeric_limits<float>::infinity();
+  float minNormalDot = 0.f; // read only with normals
+  bool targetShared = false;
+};
+inline void findClosestPoints(
+    size_t batch, size_t numSource, size_t numTarget, const float* source, const float* target, const float* sourceNormals,
+    const float* targetNormals, const ClosestPointsOptions& options, int32_t* index, float* dist2, float* points, void* stream) {
+  check(mmx_closest_points(
+      int32_t(batch), int32_t(numSource), int32_t(numTarget), source, target, options.targetShared ? 1 : 0, sourceNormals, targetNormals,
+      options.maxDist, options.minNormalDot, index, dist2, points, stream));
+}
+struct ClosestPoints {
+  std::vector<int32_t> index; // [batch][numSource], -1 = no eligible target
+  std::vector<float> dist2; // [batch][numSource], +inf where index is -1
+  std::vector<float> points; // [batch][numSource][3], zeros where index is -1
+};
+inline ClosestPoints findClosestPoints(
+    size_t batch, const std::vector<float>& source, const std::vector<float>& target, const ClosestPointsOptions& options = {},
+    const std::vector<float>& sourceNormals = {}, const std::vector<float>& targetNormals = {}) {
+  const size_t targetBatch = options.targetShared ? 1 : batch;
+  if (batch == 0 || source.empty() || target.empty() || source.size() % (3 * batch) != 0 || target.size() % (3 * targetBatch) != 0) {
+    throw std::runtime_error("momentum_amd: source must be [batch][numSource][3] and target [batch][numTarget][3] (or [numTarget][3] when shared)");
+  }
+  if (sourceNormals.empty() != targetNormals.empty() || (!sourceNormals.empty() && (sourceNormals.size() != source.size() || targetNormals.size() != target.size()))) {
+    throw std::runtime_error("momentum_amd: sourceNormals and targetNormals: both or neither, laid out like the points");
+  }
+  const size_t n = source.size() / (3 * batch), m = target.size() / (3 * targetBatch);
+  ClosestPoints r;
+  r.index.resize(batch * n);
+  r.dist2.resize(batch * n);
+  r.points.resize(batch * n * 3);
+  check(mmx_closest_points_host(
+      int32_t(batch), int32_t(n), int32_t(m), source.data(), target.data(), options.targetShared ? 1 : 0,
+      sourceNormals.empty() ? nullptr : sourceNormals.data(), targetNormals.empty() ? nullptr : targetNormals.data(), options.maxDist,
+      options.minNormalDot, r.index.data(), r.dist2.data(), r.points.data()));
+  return r;
+}
+
 class BatchedGaussNewtonSolver {
  public:
   BatchedGaussNewtonSolver(const SolverOptions& options, BatchedSkeletonSolverFunction* function) : fn_(function) {

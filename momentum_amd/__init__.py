@@ -14,5 +14,6 @@ from .rigs import (  # noqa: F401
     humanoid72_landmark_joints,
     make_test_skin,
 )
+from . import geometry  # noqa: F401  (find_closest_points)
 
-__all__ = ["Rig", "make_test_character", "make_humanoid72", "make_rig300", "humanoid72_landmark_joints", "make_test_skin"]
+__all__ = ["Rig", "make_test_character", "make_humanoid72", "make_rig300", "humanoid72_landmark_joints", "make_test_skin", "geometry"]

@@ -56,6 +56,14 @@ class SkinDesc(C.Structure):
 
 
 MMX_MAX_SKIN_INFLUENCES = 8
+# mmx_closest_points(batch, num_source, num_target, source, target, target_shared, source_normals, target_normals, max_dist,
+# min_normal_dot, index, dist2, points, stream); mmx_closest_points_host: the same without the stream
+CLOSEST_POINTS_ARGTYPES = (
+    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+)  # fmt: skip
+# mmx_closest_points_plan(batch, num_source, num_target, with_normals, &sources_per_workgroup, &target_tile, &target_ways)
+CLOSEST_POINTS_PLAN_ARGTYPES = (C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p)
 MMX_LOSS_WELSCH = float(np.finfo(np.float32).min)  # GeneralizedLossT::kWelsch
 MMX_LIMIT_MINMAX = 0  # momentum::LimitType values (character/parameter_limits.h:20-31)
 MMX_LIMIT_MINMAX_JOINT = 1

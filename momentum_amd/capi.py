@@ -34,6 +34,7 @@ SYMBOLS = [
     "mmx_eval_skeleton_state_backward", "mmx_eval_skeleton_state_backward_host",
     "mmx_skin_create", "mmx_skin_destroy", "mmx_skin_num_vertices", "mmx_skin_points", "mmx_skin_points_backward",
     "mmx_skin_points_host", "mmx_skin_points_backward_host", "mmx_host_skin_tables",
+    "mmx_closest_points", "mmx_closest_points_host", "mmx_closest_points_plan",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
     "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
@@ -111,6 +112,9 @@ def lib() -> C.CDLL:
     L.mmx_skin_points_host.argtypes = [vp, i32, vp, vp, vp]
     L.mmx_skin_points_backward_host.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.mmx_host_skin_tables.argtypes = [i32, C.POINTER(_abi.SkinDesc), _abi.c_int32_p, _abi.c_int32_p, _abi.c_int32_p, _abi.c_int32_p]
+    L.mmx_closest_points.argtypes = list(_abi.CLOSEST_POINTS_ARGTYPES)
+    L.mmx_closest_points_host.argtypes = list(_abi.CLOSEST_POINTS_ARGTYPES[:-1])
+    L.mmx_closest_points_plan.argtypes = list(_abi.CLOSEST_POINTS_PLAN_ARGTYPES)
     L.mmx_eval_jacobian_host.argtypes = [vp, vp, vp, vp, vp, i32]
     L.mmx_eval_skeleton_state_host.argtypes = [vp, vp, vp]
     L.mmx_debug_tree_normal_equations.argtypes = [vp, vp, vp, vp, vp]
@@ -265,6 +269,50 @@ def host_skin_tables(num_joints: int, joint, weight) -> dict:
     n = C.c_int32(0)
     _check(lib().mmx_host_skin_tables(int(num_joints), C.byref(d), as_ptr(start, C.c_int32), as_ptr(ev, C.c_int32), as_ptr(es, C.c_int32), C.byref(n)))
     return dict(joint_start=start, entry_vertex=ev[: n.value].copy(), entry_slot=es[: n.value].copy())
+
+
+def closest_points_plan(batch: int, num_source: int, num_target: int, with_normals: bool = False) -> dict:
+    """The launch decision of mmx_closest_points (mmx_closest_points_plan, no GPU needed): dict(sources_per_workgroup,
+    target_tile, target_ways); target_ways 1 = a tile's targets are not divided over the waves."""
+    s, t, w = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(lib().mmx_closest_points_plan(int(batch), int(num_source), int(num_target), int(bool(with_normals)), C.byref(s), C.byref(t), C.byref(w)))
+    return dict(sources_per_workgroup=s.value, target_tile=t.value, target_ways=w.value)
+
+
+def closest_points(source, target, max_dist=float("inf"), source_normals=None, target_normals=None, min_normal_dot=0.0, want_dist2=True, want_points=True):
+    """mmx_closest_points on torch device tensors, one kernel on the current stream: for every source point [B,N,3] the nearest
+    eligible target point of the same instance (target [B,M,3], or [M,3] shared by the batch).  Eligible: a finite squared
+    distance (differences first, float32) <= max_dist^2 and, with normals (both arrays or neither, laid out like the points,
+    used as given), n_s . n_t >= min_normal_dot.  Returns (index [B,N] int32 with -1 = none, dist2 [B,N] or None with +inf
+    where none, points [B,N,3] or None with zeros where none); ties go to the lowest index.  No autograd graph."""
+    import torch
+
+    def f32(t, shape, what):
+        assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), what
+        assert shape is None or tuple(t.shape) == shape, (what, tuple(t.shape), shape)
+        return t
+
+    f32(source, None, "source")
+    assert source.dim() == 3 and source.shape[2] == 3 and source.shape[0] >= 1 and source.shape[1] >= 1, "source must be [B,N,3]"
+    B, N = int(source.shape[0]), int(source.shape[1])
+    f32(target, None, "target")
+    shared = target.dim() == 2
+    assert target.dim() in (2, 3) and target.shape[-1] == 3 and target.shape[-2] >= 1, "target must be [B,M,3] or [M,3]"
+    assert shared or target.shape[0] == B, "target's batch differs from source's"
+    assert target.device == source.device
+    M = int(target.shape[-2])
+    assert (source_normals is None) == (target_normals is None), "source_normals and target_normals: both or neither"
+    if source_normals is not None:
+        f32(source_normals, tuple(source.shape), "source_normals")
+        f32(target_normals, tuple(target.shape), "target_normals")
+    with torch.cuda.device(source.device):
+        index = torch.empty((B, N), dtype=torch.int32, device=source.device)
+        dist2 = torch.empty((B, N), dtype=torch.float32, device=source.device) if want_dist2 else None
+        points = torch.empty((B, N, 3), dtype=torch.float32, device=source.device) if want_points else None
+        _check(lib().mmx_closest_points(
+            B, N, M, _dev(source), _dev(target), int(shared), _dev(source_normals), _dev(target_normals), float(max_dist), float(min_normal_dot),
+            _dev(index), _dev(dist2), _dev(points), _stream_ptr()))  # fmt: skip
+    return index, dist2, points
 
 
 def _stream_ptr() -> C.c_void_p:

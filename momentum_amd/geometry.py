@@ -1,0 +1,62 @@
+"""Geometry queries on the device, with the call shapes of pymomentum.geometry.
+
+find_closest_points is the nearest-point step of an ICP loop (mmx_closest_points: one kernel on the current stream), which
+the reference runs on the CPU.  It composes with the mesh stages: the posed vertices of momentum_amd.autograd.skin_points go
+in as points_source without leaving the device.
+"""
+from __future__ import annotations
+
+import math
+
+from . import capi
+
+__all__ = ["find_closest_points"]
+
+
+def find_closest_points(*args, max_dist: float = math.inf, min_normal_dot: float = 0.0, **kwargs):
+    """For every source point the nearest eligible target point of the same batch element.  Two forms, as in the reference:
+
+        find_closest_points(points_source, points_target, max_dist=inf)
+        find_closest_points(points_source, normals_source, points_target, normals_target, max_dist=inf, min_normal_dot=0.0)
+
+    points_source [B, N, 3] (or [N, 3]: one element), points_target [B, M, 3] or [M, 3] (shared by the batch), float32 cuda
+    tensors; the normals are laid out like their points and used as given (not renormalised).  A target is eligible when its
+    squared distance (differences first, in float32) is finite and <= max_dist^2 and, with normals,
+    n_source . n_target >= min_normal_dot; among equally near targets the lowest index wins; a NaN anywhere in a pair makes
+    the pair ineligible.  (The reference's name and default for the normal threshold are still to be confirmed: see the
+    PROVENANCE note in include/mmx.h.)
+
+    Returns (closest_points [B, N, 3] float32, zeros where invalid; index [B, N] int32, -1 where invalid; valid [B, N] bool).
+
+    The results carry no autograd graph.  Where a gradient to the target (or a differentiable distance) is wanted, gather in
+    torch: `target[b, index.long()]` on the valid rows, and take the distance to the source from that.
+    """
+    import torch
+
+    names2, names4 = ("points_source", "points_target"), ("points_source", "normals_source", "points_target", "normals_target")
+    tensors = [a for a in args if isinstance(a, torch.Tensor)]
+    rest = list(args[len(tensors) :])
+    with_normals = len(tensors) == 4 or "normals_source" in kwargs or "normals_target" in kwargs
+    names = names4 if with_normals else names2
+    given = dict(zip(names, tensors))
+    for k in names:
+        if k in kwargs:
+            assert k not in given, f"{k} given twice"
+            given[k] = kwargs.pop(k)
+    assert len(tensors) <= len(names) and set(given) == set(names), f"find_closest_points takes {names}"
+    if rest:
+        max_dist = rest.pop(0)
+    if rest and with_normals:
+        min_normal_dot = rest.pop(0)
+    assert not rest and not kwargs, "unexpected arguments"
+    src, tgt = given["points_source"], given["points_target"]
+    ns, nt = given.get("normals_source"), given.get("normals_target")
+    single = src.dim() == 2
+    prep = lambda t, lift: None if t is None else (t.detach()[None] if lift else t.detach()).contiguous()
+    index, _, points = capi.closest_points(
+        prep(src, single), prep(tgt, False), float(max_dist), prep(ns, single), prep(nt, False), float(min_normal_dot), want_dist2=False, want_points=True
+    )  # fmt: skip
+    valid = index >= 0
+    if single:
+        return points[0], index[0], valid[0]
+    return points, index, valid
