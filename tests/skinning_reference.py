@@ -7,6 +7,19 @@ sums per joint the kernel takes (vjp_np).  Checked on its own in tests/test_skin
 with (t_j, q_j, s_j) the state row [b][j] = (tx,ty,tz, qx,qy,qz,qw, s) and qrot the polynomial of mmx_device.hpp,
 p + 2 w (u x p) + 2 u x (u x p): the quaternion is used as the state holds it, never renormalised.  A zero-weight slot is
 dropped before any arithmetic (the library's rule: padding contributes nothing, whatever its joint's state holds).
+
+Per-entry error bounds (entry_bounds): for every entry of out, rest_grad and state_grad the magnitude its error is measured
+against, from the sums of absolute values of the terms that make the entry up, with u = 2^-24 (float32's unit roundoff):
+    out[b][v][c]         |x - x64| <= (K + 7) u A,   A = sum_k |w| ( sum_d |sRA_j[c][d]| |rest_d| + |(sRa_j)_c| + |t_j,c| )
+        one rounding of the posed affine M_j (built in double), at most four in a row's dot product, one product with the
+        weight and at most K accumulations: gamma_(K+6) < (K + 7) u.
+    rest_grad[b][v][c]   the same with the 3 x 3 part transposed, the cotangent in the place of rest and no translation term.
+    state_grad[b][j][c]  |x - x64| <= u |x64| + (n_j + 64) 2^-52 S,   n_j the joint's entry count and S the twelve-sum formulas
+        of vjp_np with every factor replaced by its absolute value and every subtraction by an addition: the sums are taken in
+        double from the float32 entries the reference reads and each channel is rounded once.  S = 0 asks for a zero (of
+        either sign): a joint without entries, the q channels at scale 0 or at the zero quaternion.
+tests/test_skinning_reference.py shows on the CPU that restatements of the kernels' arithmetic hold the rules and that a float32
+accumulation or a transposed N breaks the state rule.
 """
 import numpy as np
 import torch
@@ -117,6 +130,150 @@ def lbs_matrices_np(joint, weight, inverse_bind, rest, state):
         for k in range(np.asarray(joint).shape[1]):
             out[v] += float(weight[v][k]) * (mats[int(joint[v][k])] @ np.append(rest[v], 1.0))[:3]
     return out
+
+
+U32 = 2.0**-24  # float32's unit roundoff
+
+
+def _inv_np(inverse_bind, J):
+    return (np.tile(np.eye(3, 4).reshape(1, 12), (J, 1)) if inverse_bind is None else np.asarray(inverse_bind, np.float64)).reshape(J, 3, 4)
+
+
+def _entries(joint, weight):
+    """(vertex, joint, weight) of every non-zero-weight slot, in (vertex, slot) order."""
+    joint, weight = np.asarray(joint), np.asarray(weight, np.float64)
+    v, k = np.nonzero(weight != 0)
+    return v, joint[v, k].astype(np.int64), weight[v, k]
+
+
+def _rest_b(rest, B):
+    rest = np.asarray(rest, np.float64)
+    return np.broadcast_to(rest, (B,) + rest.shape[-2:]) if rest.ndim == 2 else rest
+
+
+def arbitrary_states(J, B, seed, used=None):
+    """[B, J, 8] float32 states no forward kinematics gives: translations N(0, 10); unit quaternions times a norm factor in
+    [0.5, 2] times a random sign; scales drawn from {-1.5, 2^-20, 1, 3}.  Four rows are planted on (instance, joint) pairs with
+    the joint in `used` (the joints that have entries; default: all): the zero quaternion, (0, 0, 0, w), scale exactly 0 and
+    scale -1.5 -- on distinct pairs where there are four."""
+    rng = np.random.default_rng(seed)
+    st = np.zeros((B, J, 8))
+    st[..., :3] = rng.normal(0.0, 10.0, size=(B, J, 3))
+    q = rng.normal(size=(B, J, 4))
+    q /= np.linalg.norm(q, axis=-1, keepdims=True)
+    st[..., 3:7] = q * rng.uniform(0.5, 2.0, size=(B, J, 1)) * rng.choice([-1.0, 1.0], size=(B, J, 1))
+    st[..., 7] = rng.choice([-1.5, 2.0**-20, 1.0, 3.0], size=(B, J))
+    used = np.arange(J) if used is None else np.asarray(used)
+    pairs = [(b, int(j)) for j in used for b in range(B)]
+    assert len(pairs) >= 2
+    pairs = [pairs[i] for i in rng.permutation(len(pairs))]
+    at = lambda i: pairs[i % len(pairs)]
+    st[at(0)][3:7] = 0.0
+    st[at(1)][3:6] = 0.0
+    st[at(2)][7] = 0.0
+    st[at(3)][7] = -1.5
+    return st.astype(np.float32)
+
+
+def posed_affines_np(inverse_bind, state):
+    """state [B, J, 8] -> (s R(q) A_j [B, J, 3, 3], s R(q) a_j [B, J, 3]) in float64; the posed affine is [sRA | sRa + t]."""
+    state = np.asarray(state, np.float64)
+    inv = _inv_np(inverse_bind, state.shape[1])
+    u, w, s = state[..., 3:6], state[..., 6], state[..., 7]
+    K = np.zeros(state.shape[:2] + (3, 3))
+    K[..., 0, 1], K[..., 0, 2], K[..., 1, 0], K[..., 1, 2], K[..., 2, 0], K[..., 2, 1] = -u[..., 2], u[..., 1], u[..., 2], -u[..., 0], -u[..., 1], u[..., 0]
+    R = (1.0 - 2.0 * (u * u).sum(-1))[..., None, None] * np.eye(3) + 2.0 * u[..., :, None] * u[..., None, :] + 2.0 * w[..., None, None] * K
+    sR = s[..., None, None] * R
+    return sR @ inv[:, :, :3], np.einsum("bjcd,jd->bjc", sR, inv[:, :, 3])
+
+
+def twelve_sums_np(joint, weight, inverse_bind, rest, g, J, acc=np.float64):
+    """F [B, J, 3] = sum w g and N [B, J, 3, 3] = sum w g p^T over every joint's entries, for rest [V, 3] or [B, V, 3] and
+    g [B, V, 3]: the terms in float64, accumulated entry after entry in `acc`."""
+    g = np.asarray(g, np.float64)
+    B = g.shape[0]
+    inv = _inv_np(inverse_bind, J)
+    v, je, we = _entries(joint, weight)
+    p = np.einsum("ecd,bed->bec", inv[je, :, :3], _rest_b(rest, B)[:, v]) + inv[je, :, 3]
+    wg = we[None, :, None] * g[:, v]
+    F, N = np.zeros((B, J, 3), acc), np.zeros((B, J, 3, 3), acc)
+    np.add.at(F, (slice(None), je), wg.astype(acc))
+    np.add.at(N, (slice(None), je), (wg[..., :, None] * p[..., None, :]).astype(acc))
+    return F.astype(np.float64), N.astype(np.float64)
+
+
+def state_channels_np(F, N, state):
+    """The eight channels [B, J, 8] from the twelve sums (the formulas of vjp_np), in float64."""
+    state = np.asarray(state, np.float64)
+    u, qw, s = state[..., 3:6], state[..., 6], state[..., 7]
+    tr = np.trace(N, axis1=-2, axis2=-1)
+    ax = np.stack([N[..., 2, 1] - N[..., 1, 2], N[..., 0, 2] - N[..., 2, 0], N[..., 1, 0] - N[..., 0, 1]], -1)
+    nu, ntu = np.einsum("bjcd,bjd->bjc", N, u), np.einsum("bjdc,bjd->bjc", N, u)
+    uax = (u * ax).sum(-1)
+    out = np.zeros(state.shape)
+    out[..., :3] = F
+    out[..., 3:6] = s[..., None] * (-4.0 * tr[..., None] * u + 2.0 * (nu + ntu) + 2.0 * qw[..., None] * ax)
+    out[..., 6] = s * 2.0 * uax
+    out[..., 7] = (1.0 - 2.0 * (u * u).sum(-1)) * tr + 2.0 * (u * nu).sum(-1) + 2.0 * qw * uax
+    return out
+
+
+def state_grad_np(joint, weight, inverse_bind, rest, state, g, acc=np.float64):
+    """vjp_np's state gradient for a batch, vectorised: [B, J, 8] float64; a joint without entries gets zeros whatever its row."""
+    J = np.asarray(state).shape[1]
+    F, N = twelve_sums_np(joint, weight, inverse_bind, rest, g, J, acc)
+    used = np.bincount(_entries(joint, weight)[1], minlength=J) > 0
+    st = np.where(used[None, :, None], np.asarray(state, np.float64), 0.0)
+    return np.where(used[None, :, None], state_channels_np(F, N, st), 0.0)
+
+
+def entry_bounds(joint, weight, inverse_bind, rest, state, g):
+    """The magnitudes of the per-entry rules (module docstring) for state [B, J, 8], rest [V, 3] or [B, V, 3] and the cotangent
+    g [B, V, 3]: dict(out=A [B, V, 3], rest_grad=A [B, V, 3], state_grad=S [B, J, 8], entries=n_j [J]).  Zero-weight slots are
+    omitted everywhere; a joint without entries may hold anything."""
+    state, g = np.asarray(state, np.float64), np.abs(np.asarray(g, np.float64))
+    joint, weight = np.asarray(joint), np.abs(np.asarray(weight, np.float64))
+    B, J = state.shape[:2]
+    inv = np.abs(_inv_np(inverse_bind, J))
+    r = np.abs(_rest_b(rest, B))
+    v, je, we = _entries(joint, weight)
+    n = np.bincount(je, minlength=J)
+    st = np.where((n > 0)[None, :, None], state, 0.0)
+    sRA, sRa = (np.abs(x) for x in posed_affines_np(inverse_bind, st))
+    t = np.abs(st[..., :3])
+    A_out, A_rest = np.zeros((B, len(joint), 3)), np.zeros((B, len(joint), 3))
+    np.add.at(A_out, (slice(None), v), we[None, :, None] * (np.einsum("becd,bed->bec", sRA[:, je], r[:, v]) + sRa[:, je] + t[:, je]))
+    np.add.at(A_rest, (slice(None), v), we[None, :, None] * np.einsum("bedc,bed->bec", sRA[:, je], g[:, v]))
+    # the twelve sums of absolute values and the channels with every sign turned to plus
+    p = np.einsum("ecd,bed->bec", inv[je, :, :3], r[:, v]) + inv[je, :, 3]
+    wg = we[None, :, None] * g[:, v]
+    F, N = np.zeros((B, J, 3)), np.zeros((B, J, 3, 3))
+    np.add.at(F, (slice(None), je), wg)
+    np.add.at(N, (slice(None), je), wg[..., :, None] * p[..., None, :])
+    u, qw, s = np.abs(st[..., 3:6]), np.abs(st[..., 6]), np.abs(st[..., 7])
+    tr = np.trace(N, axis1=-2, axis2=-1)
+    ax = np.stack([N[..., 2, 1] + N[..., 1, 2], N[..., 0, 2] + N[..., 2, 0], N[..., 1, 0] + N[..., 0, 1]], -1)
+    nu, ntu = np.einsum("bjcd,bjd->bjc", N, u), np.einsum("bjdc,bjd->bjc", N, u)
+    uax = (u * ax).sum(-1)
+    S = np.zeros((B, J, 8))
+    S[..., :3] = F
+    S[..., 3:6] = s[..., None] * (4.0 * tr[..., None] * u + 2.0 * (nu + ntu) + 2.0 * qw[..., None] * ax)
+    S[..., 6] = 2.0 * s * uax
+    S[..., 7] = (1.0 + 2.0 * (u * u).sum(-1)) * tr + 2.0 * (u * nu).sum(-1) + 2.0 * qw * uax
+    return dict(out=A_out, rest_grad=A_rest, state_grad=S, entries=n)
+
+
+def entry_ratios(key, got, want64, bounds, K):
+    """Per entry, the error over what its rule allows (<= 1 holds the rule; an entry whose magnitude is 0 must be a zero and
+    gets 0 or inf): out / rest_grad err / ((K + 7) u A), state_grad (err - u |x64|) / ((n_j + 64) 2^-52 S)."""
+    got, want64 = np.asarray(got, np.float64), np.asarray(want64, np.float64)
+    err = np.abs(got - want64)
+    if key == "state_grad":
+        num, den = err - U32 * np.abs(want64), (bounds["entries"][None, :, None] + 64.0) * 2.0**-52 * bounds["state_grad"]
+    else:
+        num, den = err, (K + 7) * U32 * bounds[key]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, num / np.where(den > 0, den, 1.0), np.where((got == 0) & (want64 == 0), 0.0, np.inf))
 
 
 def hand_skin(kind):

@@ -1,7 +1,10 @@
 """The joint-sorted influence list of the skinning backward pass (mmx_host_skin_tables: buildSkinTables in
 momentum_amd/csrc/mmx_skin_tables.cpp) on the CPU, bit for bit against a NumPy lexsort: every (vertex, slot) pair with a
-non-zero weight sorted by (joint, vertex, slot), joint_start [J + 1] its index -- and the refusals of the table function."""
+non-zero weight sorted by (joint, vertex, slot), joint_start [J + 1] its index -- and the refusals of the table function.  The
+wave partition and the entry weights, which that function does not return, are checked by a stand-alone C++ program."""
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -66,6 +69,18 @@ def test_eight_slots_with_a_joint_repeated_in_one_vertex():
 
 def test_negative_zero_weight_is_padding_and_a_tiny_one_is_not():
     _check(2, [[0, 1, 1]], np.array([[-0.0, 1e-45, 0.5]], np.float32))
+
+
+def test_wave_partition_and_entry_weights_under_sanitizers(tmp_path):
+    """What mmx_host_skin_tables does not return -- waveStart and entryWeight -- checked where it is built: a stand-alone
+    program (tests/cpp/test_skin_tables.cpp) that links mmx_skin_tables.cpp and nothing else."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = [os.path.join(root, "tests", "cpp", "test_skin_tables.cpp"), os.path.join(root, "momentum_amd", "csrc", "mmx_skin_tables.cpp")]
+    exe = str(tmp_path / "test_skin_tables")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout.strip().endswith("OK"), out.stdout
 
 
 def test_refusals():
