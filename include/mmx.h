@@ -1103,6 +1103,113 @@ int32_t mmx_closest_points_plan(
     int32_t* target_ways);
 
 /*
+ * Vertex normals of a batch of posed triangle meshes, and their backward pass.  The counterpart of
+ * pymomentum.geometry.compute_vertex_normals(vertex_positions, triangles) and of momentum's Mesh::updateNormals; what feeds
+ * the normals_source / normals_target arguments of mmx_closest_points from the posed vertices of mmx_skin_points without
+ * leaving the device.  Added without an ABI bump (no struct grows): a library that predates the functions lacks the symbols
+ * -- that is the feature probe.
+ *
+ * A mesh handle (mmx_mesh) holds V >= 1 vertices and T >= 1 triangles tri [T][3] (int32 vertex indices); it is static and
+ * shared by the batch.
+ *   face vector for positions p [B][V][3] and triangle t = (a, b, c):   c_t = (p_b - p_a) x (p_c - p_a)
+ *               in the triangle's own corner order and NOT normalised, so the normals are area-weighted.  It is computed by
+ *               one instruction sequence: a triangle's face vector has the same bits at each of its three vertices.  The
+ *               cross product rounds both products of a component and is never fused, so a triangle with a repeated
+ *               vertex contributes three exact zeros in any corner order.
+ *   vertex sum  m_v = sum of c_t over the incidence entries of v in ascending (triangle, corner) order (mmx_host_mesh_tables),
+ *               added by one lane in that order.  A vertex at two corners of one triangle has two entries.
+ *   normal      with s = |m_v|^2 taken in double:
+ *                 s == 0 (an isolated vertex, or only degenerate faces)   n_v = three exact zeros     h_v = 0
+ *                 s not finite                                            n_v = three NaNs            h_v = NaN
+ *                 otherwise                                               n_v = m_v / sqrt(s)         h_v = (g_v - n_v (n_v . g_v)) / |m_v|
+ *               Non-finite positions are ordinary inputs, not an error: a NaN position gives NaN normals on that vertex's
+ *               closed 1-ring and nowhere else.  A NaN normal makes every pair it is part of ineligible in
+ *               mmx_closest_points (its comparisons are ordered), which is the wanted composition; a ZERO normal has dot
+ *               product 0 with everything and is therefore ELIGIBLE at the default min_normal_dot = 0.
+ *   backward    for g = dL/dn [B][V][3] and h_v as above (from the stored sums):  H_t = (h_a + h_b) + h_c, the same bits
+ *               wherever it is used, and
+ *                 position_grad[b][x] = sum over the entries (t, corner of x) of (p_next - p_prev) x H_t
+ *               with next / prev cyclic in (a, b, c), in the same ascending entry order as the forward.  This is the exact
+ *               derivative of the forward (no term is dropped).
+ *   written     every entry of normals, sums (when not NULL) and position_grad.
+ *   refusals    before any output is touched and before the first HIP call, with a message that starts with the function's
+ *               name: MMX_ERR_INVALID_ARGUMENT for a null required pointer, V, T or batch below 1, an index outside [0, V),
+ *               3 T or B V 3 beyond 2^31 - 1, a grid beyond 2^31 - 1 workgroups; at create also for an incidence list
+ *               whose device layout (each group of 64 vertices padded to the group's highest valence) exceeds 2^31 - 1
+ *               records.
+ *   determinism a row of a result depends on that instance's positions and cotangent only -- not on the batch size, the
+ *               instance's position in the batch, or the run.  Both kernels are gathers, one lane per vertex: no atomics.
+ *   cost        a face vector is recomputed at each of its three vertices (the alternative needs scratch or atomics).  A
+ *               vertex of very high valence (the hub of a fan) is walked by ONE lane: correct, but slow.
+ * Streams and graphs: mmx_vertex_normals and mmx_vertex_normals_backward each enqueue exactly ONE kernel on `stream` and
+ * return: no memset node, no stream wait, no host read, no device scratch (which is why the backward takes sums_dev, the
+ * m_v the forward wrote, instead of recomputing a 2-ring); the tables are uploaded by mmx_mesh_create.  The calls can be
+ * captured into a HIP graph from the first call on.
+ *
+ * The _host forms take the mesh itself (sizes, host triangles, device ordinal) and host arrays instead of a handle: they
+ * refuse like mmx_mesh_create and the device forms together, still without a device, then create a handle, copy in, run,
+ * copy out, synchronise and destroy the handle -- the convenience form; a loop keeps a handle and calls the device forms.
+ *
+ * mmx_host_mesh_tables is the bookkeeping as a pure host function (no device): the vertex-sorted incidence list, every
+ * (triangle, corner) pair sorted by (vertex, triangle, corner), vertex_start [V + 1] its index; entry_triangle / entry_corner
+ * hold 3 T entries; max_valence is the longest list.  Any output may be NULL.  The kernels read this list (transposed per 64
+ * vertices) and nothing else to decide their summation order.
+ *
+ * PROVENANCE: this restates pymomentum.geometry.compute_vertex_normals(vertex_positions, triangles) and momentum's
+ * Mesh::updateNormals from memory of the reference, without a checkout at hand, so it carries no file:line citations yet.
+ * To confirm against the reference: that face vectors are area-weighted and not normalised per face; what the reference does
+ * with a NaN face (it may skip it; here it propagates); what it does with a zero sum (here: a zero normal).
+ */
+typedef struct mmx_mesh mmx_mesh;
+int32_t mmx_mesh_create(int32_t num_vertices, int32_t num_triangles, const int32_t* triangles /* [T][3] HOST */, int32_t device, mmx_mesh** out);
+void mmx_mesh_destroy(mmx_mesh* mesh);
+int32_t mmx_mesh_num_vertices(const mmx_mesh* mesh);
+int32_t mmx_mesh_num_triangles(const mmx_mesh* mesh);
+int32_t mmx_vertex_normals(
+    mmx_mesh* mesh,
+    int32_t batch,
+    const float* positions_dev /* [B][V][3] */,
+    float* normals_dev /* [B][V][3] */,
+    float* sums_dev /* NULL or [B][V][3]: m_v, what the backward reads */,
+    void* stream);
+int32_t mmx_vertex_normals_backward(
+    mmx_mesh* mesh,
+    int32_t batch,
+    const float* positions_dev,
+    const float* sums_dev /* required */,
+    const float* normal_grad_dev,
+    float* position_grad_dev,
+    void* stream);
+int32_t mmx_vertex_normals_host(
+    int32_t num_vertices,
+    int32_t num_triangles,
+    const int32_t* triangles,
+    int32_t device,
+    int32_t batch,
+    const float* positions_host,
+    float* normals_host,
+    float* sums_host /* NULL to skip */);
+int32_t mmx_vertex_normals_backward_host(
+    int32_t num_vertices,
+    int32_t num_triangles,
+    const int32_t* triangles,
+    int32_t device,
+    int32_t batch,
+    const float* positions_host,
+    const float* sums_host,
+    const float* normal_grad_host,
+    float* position_grad_host);
+int32_t mmx_host_mesh_tables(
+    int32_t num_vertices,
+    int32_t num_triangles,
+    const int32_t* triangles,
+    int32_t* vertex_start /* [V+1] */,
+    int32_t* entry_triangle,
+    int32_t* entry_corner /* up to 3T each */,
+    int32_t* num_entries,
+    int32_t* max_valence);
+
+/*
  * Numerical diagnostics of the LAST single-precision solve on this handle (one-launch and wide routes;
  * MMX_ERR_UNSUPPORTED after a solve on the explicit-Jacobian route or before the first solve): diag_dev [B][4] floats
  *   [0] the precision estimate MMX_SOLVE_PRECISION_SUSPECT is decided on (relative to |theta|)

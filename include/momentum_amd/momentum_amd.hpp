@@ -915,6 +915,79 @@ class DeviceSkin {
   size_t numVertices_ = 0;
 };
 
+// Vertex normals on a device mesh (mmx_mesh): momentum's Mesh::updateNormals / pymomentum.geometry.compute_vertex_normals for a
+// batch of posed meshes that share their triangles [T][3].  vertexNormals: positions [batch][V][3] -> unit normals
+// [batch][V][3], the normalised sum of the face vectors (p_b - p_a) x (p_c - p_a) of a vertex's triangles (area-weighted;
+// zeros where the sum is zero, NaN where it is not finite) and, for the backward pass, the unnormalised sums;
+// vertexNormalsBackward: its vector-Jacobian product.  The device forms take device pointers of the mesh's device and a
+// hipStream_t (as void*) and enqueue one kernel each on the handle the constructor uploaded; the host forms copy in, run, copy
+// out and synchronise (the convenience form: they build a handle of their own per call).
+class DeviceMesh {
+ public:
+  struct Normals {
+    std::vector<float> normals; // [batch][V][3]
+    std::vector<float> sums; // [batch][V][3], what vertexNormalsBackward reads
+  };
+  DeviceMesh(size_t numVertices, const std::vector<int32_t>& triangles, int device = 0)
+      : numVertices_(numVertices), device_(device), triangles_(triangles) {
+    if (triangles.empty() || triangles.size() % 3 != 0 || numVertices > size_t(std::numeric_limits<int32_t>::max()) ||
+        triangles.size() / 3 > size_t(std::numeric_limits<int32_t>::max())) {
+      throw std::runtime_error("momentum_amd: triangles must be [T][3] with T >= 1, and the sizes must fit int32");
+    }
+    mmx_mesh* h = nullptr;
+    check(mmx_mesh_create(int32_t(numVertices), int32_t(triangles.size() / 3), triangles.data(), int32_t(device), &h));
+    handle_.reset(h, [](mmx_mesh* p) { mmx_mesh_destroy(p); });
+  }
+  mmx_mesh* handle() const {
+    return handle_.get();
+  }
+  size_t numVertices() const {
+    return numVertices_;
+  }
+  size_t numTriangles() const {
+    return triangles_.size() / 3;
+  }
+  Normals vertexNormals(size_t batch, const std::vector<float>& positions) const {
+    checkSize(batch, positions, "positions");
+    Normals r;
+    r.normals.resize(positions.size()), r.sums.resize(positions.size());
+    check(mmx_vertex_normals_host(
+        int32_t(numVertices_), int32_t(numTriangles()), triangles_.data(), int32_t(device_), int32_t(batch), positions.data(), r.normals.data(),
+        r.sums.data()));
+    return r;
+  }
+  std::vector<float> vertexNormalsBackward(
+      size_t batch, const std::vector<float>& positions, const std::vector<float>& sums, const std::vector<float>& normalGradient) const {
+    checkSize(batch, positions, "positions");
+    checkSize(batch, sums, "sums");
+    checkSize(batch, normalGradient, "normalGradient");
+    std::vector<float> out(positions.size());
+    check(mmx_vertex_normals_backward_host(
+        int32_t(numVertices_), int32_t(numTriangles()), triangles_.data(), int32_t(device_), int32_t(batch), positions.data(), sums.data(),
+        normalGradient.data(), out.data()));
+    return out;
+  }
+  // device forms: every pointer is device memory of the mesh's device; sums may be null in the forward
+  void vertexNormals(size_t batch, const float* positions, float* normals, float* sums, void* stream) const {
+    check(mmx_vertex_normals(handle_.get(), int32_t(batch), positions, normals, sums, stream));
+  }
+  void vertexNormalsBackward(
+      size_t batch, const float* positions, const float* sums, const float* normalGradient, float* positionGradient, void* stream) const {
+    check(mmx_vertex_normals_backward(handle_.get(), int32_t(batch), positions, sums, normalGradient, positionGradient, stream));
+  }
+
+ private:
+  void checkSize(size_t batch, const std::vector<float>& a, const char* what) const {
+    if (batch == 0 || batch > size_t(std::numeric_limits<int32_t>::max()) || a.size() != batch * numVertices_ * 3) {
+      throw std::runtime_error(std::string("momentum_amd: ") + what + ".size() != batch * numVertices * 3");
+    }
+  }
+  std::shared_ptr<mmx_mesh> handle_;
+  size_t numVertices_ = 0;
+  int device_ = 0;
+  std::vector<int32_t> triangles_; // (the host forms take the mesh itself)
+};
+
 // Nearest-point queries (mmx_closest_points; pymomentum.geometry.find_closest_points, which runs on the CPU): for every
 // source point [batch][numSource][3] the nearest eligible target point of the same batch element -- targets
 // [batch][numTarget][3], or [numTarget][3] shared by the batch.  Eligible: a finite squared distance <= maxDist^2 and, with

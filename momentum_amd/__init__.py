@@ -13,7 +13,10 @@ from .rigs import (  # noqa: F401
     make_rig300,
     humanoid72_landmark_joints,
     make_test_skin,
+    make_test_mesh,
+    make_test_skinned_mesh,
 )
-from . import geometry  # noqa: F401  (find_closest_points)
+from . import geometry  # noqa: F401  (find_closest_points, compute_vertex_normals)
 
-__all__ = ["Rig", "make_test_character", "make_humanoid72", "make_rig300", "humanoid72_landmark_joints", "make_test_skin", "geometry"]
+__all__ = ["Rig", "make_test_character", "make_humanoid72", "make_rig300", "humanoid72_landmark_joints", "make_test_skin", "make_test_mesh",
+           "make_test_skinned_mesh", "geometry"]  # fmt: skip

@@ -64,6 +64,19 @@ CLOSEST_POINTS_ARGTYPES = (
 )  # fmt: skip
 # mmx_closest_points_plan(batch, num_source, num_target, with_normals, &sources_per_workgroup, &target_tile, &target_ways)
 CLOSEST_POINTS_PLAN_ARGTYPES = (C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p)
+# the vertex-normal entry points (include/mmx.h): name -> argument types, in the header's order
+_MESH = (C.c_int32, C.c_int32, c_int32_p, C.c_int32)  # num_vertices, num_triangles, triangles (host), device
+MESH_ARGTYPES = {
+    "mmx_mesh_create": _MESH + (C.POINTER(C.c_void_p),),
+    "mmx_mesh_destroy": (C.c_void_p,),
+    "mmx_mesh_num_vertices": (C.c_void_p,),
+    "mmx_mesh_num_triangles": (C.c_void_p,),
+    "mmx_vertex_normals": (C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p),
+    "mmx_vertex_normals_backward": (C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p),
+    "mmx_vertex_normals_host": _MESH + (C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p),
+    "mmx_vertex_normals_backward_host": _MESH + (C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p),
+    "mmx_host_mesh_tables": (C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p),
+}
 MMX_LOSS_WELSCH = float(np.finfo(np.float32).min)  # GeneralizedLossT::kWelsch
 MMX_LIMIT_MINMAX = 0  # momentum::LimitType values (character/parameter_limits.h:20-31)
 MMX_LIMIT_MINMAX_JOINT = 1

@@ -2,7 +2,9 @@
 pass (mmx_eval_skeleton_state_backward), the counterpart of pymomentum/backend/triton_fk.py's _forward_kernel /
 _backward_kernel pair; skin_points(skin, state) is Skin.skin_points with Skin.skin_points_backward, the counterpart of
 triton_skinning.py's pair.  Each direction of each stage is one kernel on the current stream (the rest gradient, when asked
-for, one more); nothing goes through the host.  The two compose: skin_points(skin, skeleton_state(problem, theta))."""
+for, one more); nothing goes through the host.  The two compose: skin_points(skin, skeleton_state(problem, theta)).
+vertex_normals(mesh, positions) is Mesh.vertex_normals with Mesh.vertex_normals_backward and takes the posed vertices of
+skin_points, so that normal-dependent losses reach theta."""
 from __future__ import annotations
 
 import torch
@@ -54,3 +56,27 @@ def skin_points(skin, state, rest=None):
     if not (needs and torch.is_grad_enabled()):
         return skin.skin_points(state, rest)
     return _SkinPoints.apply(state.contiguous(), rest, skin)
+
+
+class _VertexNormals(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, positions, mesh):
+        ctx.mesh = mesh
+        normals, sums = mesh.vertex_normals(positions, want_sums=True)
+        ctx.save_for_backward(positions, sums)  # the backward kernel reads the sums instead of recomputing a 2-ring
+        return normals
+
+    @staticmethod
+    def backward(ctx, grad):
+        positions, sums = ctx.saved_tensors
+        return ctx.mesh.vertex_normals_backward(positions, sums, grad.contiguous()), None
+
+
+def vertex_normals(mesh, positions):
+    """Area-weighted vertex normals [B,V,3] of positions [B,V,3] (float32, cuda, contiguous) on `mesh` (capi.Mesh),
+    differentiable with respect to the positions: one kernel forward, one backward (mmx_vertex_normals_backward, a gather
+    without atomics).  Without positions.requires_grad (or under torch.no_grad()) this is mesh.vertex_normals(positions): no
+    graph node, no sums buffer.  Composes with the other stages: vertex_normals(mesh, skin_points(skin, skeleton_state(...)))."""
+    if not (positions.requires_grad and torch.is_grad_enabled()):
+        return mesh.vertex_normals(positions)
+    return _VertexNormals.apply(positions.contiguous(), mesh)

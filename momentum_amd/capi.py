@@ -35,6 +35,8 @@ SYMBOLS = [
     "mmx_skin_create", "mmx_skin_destroy", "mmx_skin_num_vertices", "mmx_skin_points", "mmx_skin_points_backward",
     "mmx_skin_points_host", "mmx_skin_points_backward_host", "mmx_host_skin_tables",
     "mmx_closest_points", "mmx_closest_points_host", "mmx_closest_points_plan",
+    "mmx_mesh_create", "mmx_mesh_destroy", "mmx_mesh_num_vertices", "mmx_mesh_num_triangles", "mmx_vertex_normals",
+    "mmx_vertex_normals_backward", "mmx_vertex_normals_host", "mmx_vertex_normals_backward_host", "mmx_host_mesh_tables",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
     "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
@@ -115,6 +117,9 @@ def lib() -> C.CDLL:
     L.mmx_closest_points.argtypes = list(_abi.CLOSEST_POINTS_ARGTYPES)
     L.mmx_closest_points_host.argtypes = list(_abi.CLOSEST_POINTS_ARGTYPES[:-1])
     L.mmx_closest_points_plan.argtypes = list(_abi.CLOSEST_POINTS_PLAN_ARGTYPES)
+    for name, types in _abi.MESH_ARGTYPES.items():
+        getattr(L, name).argtypes = list(types)
+    L.mmx_mesh_destroy.restype = None
     L.mmx_eval_jacobian_host.argtypes = [vp, vp, vp, vp, vp, i32]
     L.mmx_eval_skeleton_state_host.argtypes = [vp, vp, vp]
     L.mmx_debug_tree_normal_equations.argtypes = [vp, vp, vp, vp, vp]
@@ -271,6 +276,29 @@ def host_skin_tables(num_joints: int, joint, weight) -> dict:
     return dict(joint_start=start, entry_vertex=ev[: n.value].copy(), entry_slot=es[: n.value].copy())
 
 
+def _triangles(triangles) -> np.ndarray:
+    """[T,3] int32 C-contiguous host copy of a triangle list (a tensor on any device, an array, nested lists)."""
+    if hasattr(triangles, "detach"):
+        triangles = triangles.detach().cpu().numpy()
+    tri = np.asarray(triangles)
+    assert tri.ndim == 2 and tri.shape[1] == 3 and tri.dtype.kind in "iu", "triangles must be integers [T,3]"
+    assert tri.size == 0 or (tri.min() >= -(2**31) and tri.max() < 2**31), "triangle indices must fit int32"
+    return np.ascontiguousarray(tri, dtype=np.int32)
+
+
+def host_mesh_tables(num_vertices: int, triangles) -> dict:
+    """The vertex-sorted incidence list of the vertex-normal kernels (mmx_host_mesh_tables, no GPU needed): every (triangle,
+    corner) pair sorted by (vertex, triangle, corner): dict(vertex_start [V+1], entry_triangle, entry_corner, max_valence)."""
+    tri = _triangles(triangles)
+    start = np.zeros(int(num_vertices) + 1, np.int32)
+    et, ec = (np.zeros(max(tri.size, 1), np.int32) for _ in range(2))
+    n, mv = C.c_int32(0), C.c_int32(0)
+    _check(lib().mmx_host_mesh_tables(
+        int(num_vertices), tri.shape[0], as_ptr(tri, C.c_int32), as_ptr(start, C.c_int32), as_ptr(et, C.c_int32), as_ptr(ec, C.c_int32),
+        C.byref(n), C.byref(mv)))  # fmt: skip
+    return dict(vertex_start=start, entry_triangle=et[: n.value].copy(), entry_corner=ec[: n.value].copy(), max_valence=int(mv.value))
+
+
 def closest_points_plan(batch: int, num_source: int, num_target: int, with_normals: bool = False) -> dict:
     """The launch decision of mmx_closest_points (mmx_closest_points_plan, no GPU needed): dict(sources_per_workgroup,
     target_tile, target_ways); target_ways 1 = a tile's targets are not divided over the waves."""
@@ -422,6 +450,75 @@ class Skin:
             self._f32(rest_grad, (B, self.V, 3), "rest_grad")
         _check(lib().mmx_skin_points_backward(self._h, B, _dev(state), _dev(rest), _dev(grad_out), _dev(state_grad), _dev(rest_grad), _stream_ptr()))
         return state_grad, rest_grad
+
+
+class Mesh:
+    """A triangle mesh on a device (mmx_mesh): area-weighted vertex normals of posed vertices [B,V,3] and their backward
+    pass.  triangles [T,3] integers (host or device; copied once), num_vertices V.  The counterpart of
+    pymomentum.geometry.compute_vertex_normals / Mesh::updateNormals; one kernel per call on the current stream."""
+
+    def __init__(self, triangles, num_vertices: int, device: int = 0):
+        import torch
+
+        tri = _triangles(triangles)
+        self.V, self.T = int(num_vertices), int(tri.shape[0])
+        self.device = torch.device("cuda", int(device))
+        self._h = C.c_void_p(0)
+        _check(lib().mmx_mesh_create(self.V, self.T, as_ptr(tri, C.c_int32), int(device), C.byref(self._h)))
+
+    def close(self) -> None:
+        if self._h:
+            lib().mmx_mesh_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _f32(self, t, B, what):
+        import torch
+
+        assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), what
+        assert tuple(t.shape) == (B, self.V, 3), (what, tuple(t.shape), (B, self.V, 3))
+        return t
+
+    def _batch(self, positions) -> int:
+        import torch
+
+        assert isinstance(positions, torch.Tensor) and positions.dim() == 3 and positions.shape[0] >= 1, "positions must be [B,V,3]"
+        B = int(positions.shape[0])
+        self._f32(positions, B, "positions")
+        return B
+
+    def vertex_normals(self, positions, want_sums=False, out=None):
+        """Normals [B,V,3] float32 of positions [B,V,3] (float32, cuda, contiguous): the normalised sum of the face vectors
+        (p_b - p_a) x (p_c - p_a) of a vertex's triangles; exact zeros where that sum is zero, NaN where it is not finite.
+        want_sums: (normals, sums), the unnormalised sums the backward pass reads."""
+        import torch
+
+        B = self._batch(positions)
+        if out is None:
+            out = torch.empty((B, self.V, 3), dtype=torch.float32, device=self.device)
+        self._f32(out, B, "out")
+        sums = torch.empty((B, self.V, 3), dtype=torch.float32, device=self.device) if want_sums else None
+        _check(lib().mmx_vertex_normals(self._h, B, _dev(positions), _dev(out), _dev(sums), _stream_ptr()))
+        return (out, sums) if want_sums else out
+
+    def vertex_normals_backward(self, positions, sums, grad_normals, out=None):
+        """dL/dpositions [B,V,3] for grad_normals = dL/dnormals [B,V,3] and the forward's sums: a gather in a fixed order,
+        without atomics.  Every entry is written."""
+        import torch
+
+        B = self._batch(positions)
+        self._f32(sums, B, "sums")
+        self._f32(grad_normals, B, "grad_normals")
+        if out is None:
+            out = torch.empty((B, self.V, 3), dtype=torch.float32, device=self.device)
+        self._f32(out, B, "out")
+        _check(lib().mmx_vertex_normals_backward(self._h, B, _dev(positions), _dev(sums), _dev(grad_normals), _dev(out), _stream_ptr()))
+        return out
 
 
 # Route every Problem created from here on starts with ("auto" | "fused" | "wide" | "explicit_jacobian" | "wave"): the parity tests

@@ -2,7 +2,8 @@
 
 find_closest_points is the nearest-point step of an ICP loop (mmx_closest_points: one kernel on the current stream), which
 the reference runs on the CPU.  It composes with the mesh stages: the posed vertices of momentum_amd.autograd.skin_points go
-in as points_source without leaving the device.
+in as points_source without leaving the device.  compute_vertex_normals (mmx_vertex_normals, differentiable) makes the
+normals of those vertices that the overload with normals takes.
 """
 from __future__ import annotations
 
@@ -10,7 +11,32 @@ import math
 
 from . import capi
 
-__all__ = ["find_closest_points"]
+__all__ = ["find_closest_points", "compute_vertex_normals"]
+
+
+def compute_vertex_normals(vertex_positions, triangles):
+    """Area-weighted vertex normals of a batch of posed meshes, the call shape of
+    pymomentum.geometry.compute_vertex_normals(vertex_positions, triangles).
+
+    vertex_positions [B, V, 3] (or [V, 3]: one element), a float32 cuda tensor; triangles a capi.Mesh, or an integer tensor /
+    array [T, 3].  With a capi.Mesh this is the loop form: the handle's tables are on the device already and the call is one
+    kernel.  With a tensor / array it is the convenience form: a handle is built for the call, which costs a host copy of the
+    triangles, the incidence sort and an upload every time.
+
+    A normal is the normalised sum of the face vectors (p_b - p_a) x (p_c - p_a) of the vertex's triangles (not normalised
+    per face); a vertex of no triangle or of degenerate ones only gets zeros, a vertex next to a NaN position NaN.
+    Differentiable with respect to vertex_positions (momentum_amd.autograd.vertex_normals); returns the shape it was given.
+    """
+    from . import autograd
+
+    single = vertex_positions.dim() == 2
+    pos = (vertex_positions[None] if single else vertex_positions).contiguous()
+    assert pos.dim() == 3 and pos.shape[2] == 3, "vertex_positions must be [B, V, 3] or [V, 3]"
+    own = not isinstance(triangles, capi.Mesh)
+    mesh = capi.Mesh(triangles, int(pos.shape[1]), device=pos.device.index or 0) if own else triangles
+    normals = autograd.vertex_normals(mesh, pos)
+    # (a handle built here stays alive in the graph node until the backward pass has run; without a graph it goes now)
+    return normals[0] if single else normals
 
 
 def find_closest_points(*args, max_dist: float = math.inf, min_normal_dot: float = 0.0, **kwargs):

@@ -375,26 +375,11 @@ class TestSkin:
     rest: np.ndarray  # [V,3] float32
 
 
-def make_test_skin(rig: Rig, num_vertices: int, max_influences: int, seed: int, random_affine: bool = False) -> TestSkin:
-    """Synthetic skin for tests and scripts/skinning_rate.py: vertices scattered around the rest pose's bones, each bound to its
-    nearest joint and that joint's tree neighbours (parent, then children) with positive weights that sum to 1; unused slots
-    carry weight 0 (and the nearest joint's index).  inverse_bind is the float64 inverse of the rest-pose world transforms;
-    random_affine perturbs every entry of it, so that the full 3 x 4 is exercised."""
-    rng = np.random.default_rng(seed)
-    J, V, K = rig.num_joints, int(num_vertices), int(max_influences)
-    assert V >= 1 and 1 <= K <= 8
-    world = rest_pose_transforms(rig)
-    pos = world[:, :, 3]
-    children: List[List[int]] = [[] for _ in range(J)]
-    for j in range(1, J):
-        if rig.parent[j] >= 0:
-            children[int(rig.parent[j])].append(j)
-    bone = np.array([np.linalg.norm(pos[j] - pos[int(rig.parent[j])]) if rig.parent[j] >= 0 else 0.0 for j in range(J)])
-    spread = 0.25 * (bone[bone > 0].mean() if (bone > 0).any() else 1.0)
-    at = np.sort(rng.integers(0, J, size=V))  # bone by bone: neighbours in the vertex order share joints, as a mesh's do
-    along = rng.uniform(0.0, 1.0, size=V)
-    par = np.where(rig.parent[at] >= 0, rig.parent[at], at)
-    rest = pos[at] + along[:, None] * (pos[par] - pos[at]) + spread * rng.normal(size=(V, 3))
+def _bind_vertices(rig: Rig, pos: np.ndarray, children: List[List[int]], spread: float, rest: np.ndarray, K: int):
+    """make_test_skin's weighting rule: (joint [V,K] int32, weight [V,K] float32) of rest positions [V,3] -- the nearest joint
+    and its tree neighbours (parent, then children), weights 1 / (spread + distance) normalised to sum 1, unused slots weight
+    0 on the nearest joint."""
+    V = rest.shape[0]
     joint = np.zeros((V, K), np.int32)
     weight = np.zeros((V, K), np.float32)
     for v in range(V):
@@ -405,10 +390,97 @@ def make_test_skin(rig: Rig, num_vertices: int, max_influences: int, seed: int, 
         w = (w / w.sum()).astype(np.float32)
         joint[v], joint[v, : len(cand)] = near, cand
         weight[v, : len(cand)] = w
+    return joint, weight
+
+
+def _inverse_bind(world: np.ndarray) -> np.ndarray:
+    """Float64 inverses [J,3,4] of the 3 x 4 affines `world`."""
+    J = world.shape[0]
     inv = np.zeros((J, 3, 4))
     for j in range(J):
         A = np.linalg.inv(world[j, :, :3])
         inv[j, :, :3], inv[j, :, 3] = A, -A @ world[j, :, 3]
+    return inv
+
+
+def _rig_neighbourhood(rig: Rig, pos: np.ndarray):
+    """(children lists, spread = a quarter of the mean bone length) of a rig with rest-pose joint positions pos."""
+    J = rig.num_joints
+    children: List[List[int]] = [[] for _ in range(J)]
+    for j in range(1, J):
+        if rig.parent[j] >= 0:
+            children[int(rig.parent[j])].append(j)
+    bone = np.array([np.linalg.norm(pos[j] - pos[int(rig.parent[j])]) if rig.parent[j] >= 0 else 0.0 for j in range(J)])
+    spread = 0.25 * (bone[bone > 0].mean() if (bone > 0).any() else 1.0)
+    return children, spread
+
+
+def make_test_skin(rig: Rig, num_vertices: int, max_influences: int, seed: int, random_affine: bool = False) -> TestSkin:
+    """Synthetic skin for tests and scripts/skinning_rate.py: vertices scattered around the rest pose's bones, each bound to its
+    nearest joint and that joint's tree neighbours (parent, then children) with positive weights that sum to 1; unused slots
+    carry weight 0 (and the nearest joint's index).  inverse_bind is the float64 inverse of the rest-pose world transforms;
+    random_affine perturbs every entry of it, so that the full 3 x 4 is exercised."""
+    rng = np.random.default_rng(seed)
+    J, V, K = rig.num_joints, int(num_vertices), int(max_influences)
+    assert V >= 1 and 1 <= K <= 8
+    world = rest_pose_transforms(rig)
+    pos = world[:, :, 3]
+    children, spread = _rig_neighbourhood(rig, pos)
+    at = np.sort(rng.integers(0, J, size=V))  # bone by bone: neighbours in the vertex order share joints, as a mesh's do
+    along = rng.uniform(0.0, 1.0, size=V)
+    par = np.where(rig.parent[at] >= 0, rig.parent[at], at)
+    rest = pos[at] + along[:, None] * (pos[par] - pos[at]) + spread * rng.normal(size=(V, 3))
+    joint, weight = _bind_vertices(rig, pos, children, spread, rest, K)
+    inv = _inverse_bind(world)
     if random_affine:
         inv += 0.1 * rng.normal(size=inv.shape)
     return TestSkin(joint, weight, inv.reshape(J, 12).astype(np.float32), rest.astype(np.float32))
+
+
+@dataclass
+class TestMesh:
+    """A triangle mesh for capi.Mesh(triangles, num_vertices): positions [V,3] float32 and triangles [T,3] int32."""
+
+    __test__ = False  # (not a pytest class)
+    positions: np.ndarray
+    triangles: np.ndarray
+
+
+def make_test_mesh(nu: int, nv: int, noise: float, seed: int, offset=(0.0, 0.0, 0.0)) -> TestMesh:
+    """Synthetic closed mesh for tests and scripts/vertex_normals_rate.py: a torus (major radius 0.3 around z, minor radius 0.1)
+    as an nu x nv grid, vertex i * nv + j at major angle 2 pi i / nu and minor angle 2 pi j / nv, every quad split along the same
+    diagonal into two outward-facing triangles: V = nu nv vertices of valence 6, T = 2 nu nv triangles.  Every coordinate is
+    then jittered by a uniform draw from +-noise x the shortest grid edge, and `offset` is added."""
+    nu, nv = int(nu), int(nv)
+    assert nu >= 3 and nv >= 3
+    rng = np.random.default_rng(seed)
+    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+    th, ph = 2.0 * np.pi * i.reshape(-1) / nu, 2.0 * np.pi * j.reshape(-1) / nv
+    ring = 0.3 + 0.1 * np.cos(ph)
+    pos = np.stack([ring * np.cos(th), ring * np.sin(th), 0.1 * np.sin(ph)], axis=1)
+    at = lambda a, b: ((a % nu) * nv + (b % nv)).reshape(-1)
+    v00, v10, v11, v01 = at(i, j), at(i + 1, j), at(i + 1, j + 1), at(i, j + 1)
+    tri = np.stack([np.stack([v00, v10, v11], axis=1), np.stack([v00, v11, v01], axis=1)], axis=1).reshape(-1, 3).astype(np.int32)
+    edges = np.concatenate([pos[tri[:, 1]] - pos[tri[:, 0]], pos[tri[:, 2]] - pos[tri[:, 1]], pos[tri[:, 0]] - pos[tri[:, 2]]])
+    shortest = float(np.linalg.norm(edges, axis=1).min())
+    pos = pos + float(noise) * shortest * rng.uniform(-1.0, 1.0, size=pos.shape) + np.asarray(offset, np.float64)
+    return TestMesh(pos.astype(np.float32), tri)
+
+
+def make_test_skinned_mesh(rig: Rig, nu: int, nv: int, max_influences: int, seed: int) -> Tuple[TestSkin, np.ndarray]:
+    """(TestSkin, triangles [T,3] int32): the make_test_mesh torus (noise 0.1) bound to `rig` with make_test_skin's weighting
+    rule.  The torus is scaled uniformly so that its diameter spans the longest side of the bounding box of the rest pose's
+    joints and centred on that box."""
+    K = int(max_influences)
+    assert 1 <= K <= 8
+    mesh = make_test_mesh(nu, nv, 0.1, seed)
+    world = rest_pose_transforms(rig)
+    pos = world[:, :, 3]
+    lo, hi = pos.min(axis=0), pos.max(axis=0)
+    side = float((hi - lo).max())
+    scale = (side if side > 0 else 1.0) / 0.8
+    rest = 0.5 * (lo + hi) + scale * mesh.positions.astype(np.float64)
+    children, spread = _rig_neighbourhood(rig, pos)
+    joint, weight = _bind_vertices(rig, pos, children, spread, rest, K)
+    inv = _inverse_bind(world)
+    return TestSkin(joint, weight, inv.reshape(rig.num_joints, 12).astype(np.float32), rest.astype(np.float32)), mesh.triangles
