@@ -1210,6 +1210,110 @@ int32_t mmx_host_mesh_tables(
     int32_t* max_valence);
 
 /*
+ * Closest points ON a posed triangle mesh (point-to-surface): for every source point of every instance, the nearest point
+ * of the nearest eligible triangle of the same instance's mesh, with its face index and barycentric coordinates.  The
+ * counterpart of pymomentum.geometry.find_closest_points_on_mesh, which runs on the CPU; the last stage of
+ * skeleton_state -> skin_points -> closest points in a registration loop, where the residual slides along the surface and a
+ * gradient reaches all three vertices of the face.  Added without an ABI bump (no struct grows): a library that predates
+ * the functions lacks the symbols -- that is the feature probe.  All arrays are float32 (indices int32) on the mesh's device.
+ *
+ * For source p and triangle f = (a, b, c) of the handle's list, vertices [B][V][3] (or one shared [V][3]):
+ *   record      (per triangle, one function)  e1 = b - a, e2 = c - a, float32 differences; the face vector n = e1 x e2 as
+ *               mmx_vertex_normals computes it (both products of a component rounded, never fused), here in float32;
+ *                 d11 = dot(e1, e1)  d12 = dot(e2, e1)  d22 = dot(e2, e2)     dot(u, w) = fma(u.z, w.z, fma(u.y, w.y, u.x * w.x))
+ *                 i11 = 1 / d11   i22 = 1 / d22   ibc = 1 / ((d11 - d12) + (d22 - d12))
+ *               (correctly rounded divisions).  The triangle is INELIGIBLE FOR EVERY SOURCE when n is three exact zeros
+ *               (a repeated vertex index gives that) or when any of the fifteen record values is not finite.
+ *   pair        (per source and triangle, one function)  v = p - a taken FIRST, in float32; then the region form of
+ *               Ericson, Real-Time Collision Detection 5.1.5, branch-free (selects applied in reverse order of priority):
+ *                 d1 = dot(e1, v)  d2 = dot(e2, v)  d3 = d1 - d11  d4 = d2 - d12  d5 = d1 - d12  d6 = d2 - d22
+ *                 vc = fma(d1, d4, -(d3 * d2))   vb = fma(d5, d2, -(d1 * d6))   va = fma(d3, d6, -(d5 * d4))
+ *                 (s, t) = (vb * den, vc * den), den = rcp((va + vb) + vc)                   the interior (rcp: the hardware
+ *                                                                                            reciprocal, within 1 ulp)
+ *                        = (1 - w, w), w = (d4 - d3) * ibc   if va <= 0, d4 - d3 >= 0, d5 - d6 >= 0    edge bc
+ *                        = (0, d2 * i22)                     if vb <= 0, d2 >= 0, d6 <= 0              edge ac
+ *                        = (0, 1)                            if d6 >= 0, d5 <= d6                      vertex c
+ *                        = (d1 * i11, 0)                     if vc <= 0, d1 >= 0, d3 <= 0              edge ab
+ *                        = (1, 0)                            if d3 >= 0, d4 <= d3                      vertex b
+ *                        = (0, 0)                            if d1 <= 0, d2 <= 0                       vertex a
+ *                 (the LAST line that applies wins), then with q(x) = 1 - (1 - x), which rounds x in [0, 1] to a multiple of
+ *                 2^-24:  s = q(min(max(s, 0), 1)),  t = q(min(max(t, 0), 1 - s)).  That moves the point by less than a unit in
+ *                 the last place of an edge and makes 1 - s and (1 - s) - t exact: the weights sum to 1 without rounding.  Then
+ *                 r = fma(-t, e2, fma(-s, e1, v))  per component,   dist2 = fma(r.z, r.z, fma(r.y, r.y, r.x * r.x)).
+ *               dist2 is |r|^2 of the RESIDUAL VECTOR; the expanded quadratic |v|^2 - 2 s (e1.v) - ... is not used anywhere
+ *               (in float32 it is wrong by thousands of units in the last place of the pair's scale near the surface).
+ *               Every pair goes through this instruction sequence and no other, whichever lane, wave, tile or remainder
+ *               handles it (no contraction is left to the compiler), so two identical triangles compute identical bits.
+ *   eligible    dist2 is finite and dist2 <= max_dist * max_dist (the product taken in float32: +inf stays +inf).  Every
+ *               comparison is ordered, so a NaN or an infinity anywhere in a pair makes the pair ineligible.  Non-finite
+ *               sources and vertices are ordinary inputs, not errors.
+ *   result      the eligible triangle with the smallest computed dist2; among equal dist2 the lowest face index.
+ *               face_index [B][N] is -1 where nothing is eligible; barycentric [B][N][3] = (w_a, w_b, w_c) with w_b = s,
+ *               w_c = t, w_a = (1 - s) - t (exact; each >= 0 by the clamps above); points [B][N][3] = fma(t, e2, fma(s, e1, a))
+ *               per component; dist2 [B][N] the winning computed dist2.  Where face_index is -1 the barycentrics and the
+ *               points are zeros and dist2 is +inf.  Every entry of every non-NULL output is written.
+ *   sharing     vertices_shared != 0: one [V][3] array serves every instance; the result is bit-identical to the same
+ *               vertices replicated per instance.
+ *   refusals    before any output is touched and before the first HIP call, with a message that starts with the function's
+ *               name: MMX_ERR_INVALID_ARGUMENT for a null required pointer (mesh, source, vertices, face_index), batch or
+ *               num_source below 1, max_dist negative or NaN, a launch grid beyond 2^31 - 1 workgroups; the _host form also
+ *               for what mmx_mesh_create refuses.
+ *   determinism a row of a result depends on that instance's inputs only -- not on the batch size, the instance's position
+ *               in the batch, or the run.  No atomics: a lane scans its faces in ascending order with a strict <, and the
+ *               partial results of the waves that share a tile are combined by the lexicographic minimum of (dist2, face).
+ * Streams and graphs: mmx_closest_points_on_mesh enqueues ONE kernel on `stream` and returns: no memset node, no stream wait,
+ * no host read, no device scratch, no kernel attribute to raise (38 KB of LDS).  The triangle list is uploaded by
+ * mmx_mesh_create.  The call can be captured into a HIP graph from the first call on.  The _host form takes the mesh itself
+ * (sizes, host triangles, device ordinal) and host arrays like mmx_vertex_normals_host: it refuses without a device, then
+ * creates a handle, copies in, runs, copies out, synchronises and destroys the handle.
+ *
+ * mmx_closest_points_on_mesh_plan is the launch decision as a pure host function (no device), the one the launcher itself
+ * calls: how many sources a workgroup owns, how many triangles a staged LDS tile holds, and over how many waves a tile's
+ * triangles are divided.  MMX_ERR_INVALID_ARGUMENT for a size below 1 or a grid beyond 2^31 - 1; any output may be NULL.
+ *
+ * PROVENANCE: this restates pymomentum.geometry.find_closest_points_on_mesh(points_source, vertices_target, faces_target) ->
+ * (valid, closest_points, face_index, barycentric) from memory of the reference, without a checkout at hand, so it carries no
+ * file:line citations yet.  To confirm against the reference: the order of the returned tuple; the order of the barycentric
+ * weights (here the face's own corner order a, b, c); what the reference does with degenerate faces (here they are never
+ * returned); and that it has no max_dist (here an extension; +inf reproduces a call without it).
+ */
+int32_t mmx_closest_points_on_mesh(
+    mmx_mesh* mesh,
+    int32_t batch,
+    int32_t num_source,
+    const float* source_dev /* [B][N][3] */,
+    const float* vertices_dev /* [B][V][3], or [V][3] when vertices_shared != 0 */,
+    int32_t vertices_shared,
+    float max_dist /* >= 0, +inf allowed */,
+    int32_t* face_index_dev /* [B][N], -1 = no eligible triangle */,
+    float* barycentric_dev /* NULL or [B][N][3], zeros where face_index is -1 */,
+    float* points_dev /* NULL or [B][N][3], zeros where face_index is -1 */,
+    float* dist2_dev /* NULL or [B][N], +inf where face_index is -1 */,
+    void* stream);
+int32_t mmx_closest_points_on_mesh_host(
+    int32_t num_vertices,
+    int32_t num_triangles,
+    const int32_t* triangles,
+    int32_t device,
+    int32_t batch,
+    int32_t num_source,
+    const float* source_host,
+    const float* vertices_host,
+    int32_t vertices_shared,
+    float max_dist,
+    int32_t* face_index_host,
+    float* barycentric_host /* NULL to skip */,
+    float* points_host /* NULL to skip */,
+    float* dist2_host /* NULL to skip */);
+int32_t mmx_closest_points_on_mesh_plan(
+    int32_t batch,
+    int32_t num_source,
+    int32_t num_triangles,
+    int32_t* sources_per_workgroup,
+    int32_t* triangle_tile,
+    int32_t* triangle_ways);
+
+/*
  * Numerical diagnostics of the LAST single-precision solve on this handle (one-launch and wide routes;
  * MMX_ERR_UNSUPPORTED after a solve on the explicit-Jacobian route or before the first solve): diag_dev [B][4] floats
  *   [0] the precision estimate MMX_SOLVE_PRECISION_SUSPECT is decided on (relative to |theta|)

@@ -915,6 +915,18 @@ class DeviceSkin {
   size_t numVertices_ = 0;
 };
 
+// Closest points ON a posed mesh (DeviceMesh::closestPoints / findClosestPointsOnMesh below)
+struct ClosestPointsOnMeshOptions {
+  float maxDist = std::numeric_limits<float>::infinity();
+  bool verticesShared = false; // vertices are [V][3], shared by the batch
+};
+struct ClosestPointsOnMesh {
+  std::vector<int32_t> faceIndex; // [batch][numSource], -1 = no eligible triangle
+  std::vector<float> barycentric; // [batch][numSource][3] = (w_a, w_b, w_c), zeros where faceIndex is -1
+  std::vector<float> points; // [batch][numSource][3], zeros where faceIndex is -1
+  std::vector<float> dist2; // [batch][numSource], +inf where faceIndex is -1
+};
+
 // Vertex normals on a device mesh (mmx_mesh): momentum's Mesh::updateNormals / pymomentum.geometry.compute_vertex_normals for a
 // batch of posed meshes that share their triangles [T][3].  vertexNormals: positions [batch][V][3] -> unit normals
 // [batch][V][3], the normalised sum of the face vectors (p_b - p_a) x (p_c - p_a) of a vertex's triangles (area-weighted;
@@ -967,7 +979,34 @@ class DeviceMesh {
         normalGradient.data(), out.data()));
     return out;
   }
-  // device forms: every pointer is device memory of the mesh's device; sums may be null in the forward
+  // Closest points ON the posed mesh (mmx_closest_points_on_mesh; pymomentum.geometry.find_closest_points_on_mesh, which runs on
+  // the CPU): for every source point [batch][numSource][3] the nearest point of the nearest eligible triangle of the same batch
+  // element's vertices [batch][V][3] (or [V][3] shared), with its face index and barycentric weights.  A triangle with a
+  // repeated vertex or a non-finite vertex is never returned; ties go to the lowest face index.
+  ClosestPointsOnMesh closestPoints(
+      size_t batch, const std::vector<float>& source, const std::vector<float>& vertices, const ClosestPointsOnMeshOptions& options = {}) const {
+    checkSize(options.verticesShared ? 1 : batch, vertices, "vertices");
+    if (batch == 0 || batch > size_t(std::numeric_limits<int32_t>::max()) || source.empty() || source.size() % (3 * batch) != 0) {
+      throw std::runtime_error("momentum_amd: source must be [batch][numSource][3]");
+    }
+    const size_t n = source.size() / (3 * batch);
+    ClosestPointsOnMesh r;
+    r.faceIndex.resize(batch * n), r.barycentric.resize(batch * n * 3), r.points.resize(batch * n * 3), r.dist2.resize(batch * n);
+    check(mmx_closest_points_on_mesh_host(
+        int32_t(numVertices_), int32_t(numTriangles()), triangles_.data(), int32_t(device_), int32_t(batch), int32_t(n), source.data(),
+        vertices.data(), options.verticesShared ? 1 : 0, options.maxDist, r.faceIndex.data(), r.barycentric.data(), r.points.data(),
+        r.dist2.data()));
+    return r;
+  }
+  // device forms: every pointer is device memory of the mesh's device; sums may be null in the forward; barycentric, points and
+  // dist2 may be null in closestPoints
+  void closestPoints(
+      size_t batch, size_t numSource, const float* source, const float* vertices, const ClosestPointsOnMeshOptions& options, int32_t* faceIndex,
+      float* barycentric, float* points, float* dist2, void* stream) const {
+    check(mmx_closest_points_on_mesh(
+        handle_.get(), int32_t(batch), int32_t(numSource), source, vertices, options.verticesShared ? 1 : 0, options.maxDist, faceIndex, barycentric,
+        points, dist2, stream));
+  }
   void vertexNormals(size_t batch, const float* positions, float* normals, float* sums, void* stream) const {
     check(mmx_vertex_normals(handle_.get(), int32_t(batch), positions, normals, sums, stream));
   }
@@ -1032,6 +1071,13 @@ inline ClosestPoints findClosestPoints(
       sourceNormals.empty() ? nullptr : sourceNormals.data(), targetNormals.empty() ? nullptr : targetNormals.data(), options.maxDist,
       options.minNormalDot, r.index.data(), r.dist2.data(), r.points.data()));
   return r;
+}
+
+// ... and ON a posed mesh: the call shape of pymomentum.geometry.find_closest_points_on_mesh (DeviceMesh::closestPoints)
+inline ClosestPointsOnMesh findClosestPointsOnMesh(
+    const DeviceMesh& mesh, size_t batch, const std::vector<float>& source, const std::vector<float>& vertices,
+    const ClosestPointsOnMeshOptions& options = {}) {
+  return mesh.closestPoints(batch, source, vertices, options);
 }
 
 class BatchedGaussNewtonSolver {

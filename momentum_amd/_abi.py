@@ -77,6 +77,19 @@ MESH_ARGTYPES = {
     "mmx_vertex_normals_backward_host": _MESH + (C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p),
     "mmx_host_mesh_tables": (C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p),
 }
+# the closest-points-on-mesh entry points (include/mmx.h): name -> argument types, in the header's order
+CLOSEST_POINTS_ON_MESH_ARGTYPES = {
+    # (mesh, batch, num_source, source, vertices, vertices_shared, max_dist, face_index, barycentric, points, dist2, stream)
+    "mmx_closest_points_on_mesh": (
+        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+    ),
+    # (the mesh itself, batch, num_source, source, vertices, vertices_shared, max_dist, face_index, barycentric, points, dist2)
+    "mmx_closest_points_on_mesh_host": _MESH + (
+        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+    ),
+    # (batch, num_source, num_triangles, &sources_per_workgroup, &triangle_tile, &triangle_ways)
+    "mmx_closest_points_on_mesh_plan": (C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p),
+}  # fmt: skip
 MMX_LOSS_WELSCH = float(np.finfo(np.float32).min)  # GeneralizedLossT::kWelsch
 MMX_LIMIT_MINMAX = 0  # momentum::LimitType values (character/parameter_limits.h:20-31)
 MMX_LIMIT_MINMAX_JOINT = 1

@@ -37,6 +37,7 @@ SYMBOLS = [
     "mmx_closest_points", "mmx_closest_points_host", "mmx_closest_points_plan",
     "mmx_mesh_create", "mmx_mesh_destroy", "mmx_mesh_num_vertices", "mmx_mesh_num_triangles", "mmx_vertex_normals",
     "mmx_vertex_normals_backward", "mmx_vertex_normals_host", "mmx_vertex_normals_backward_host", "mmx_host_mesh_tables",
+    "mmx_closest_points_on_mesh", "mmx_closest_points_on_mesh_host", "mmx_closest_points_on_mesh_plan",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
     "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
@@ -120,6 +121,8 @@ def lib() -> C.CDLL:
     for name, types in _abi.MESH_ARGTYPES.items():
         getattr(L, name).argtypes = list(types)
     L.mmx_mesh_destroy.restype = None
+    for name, types in _abi.CLOSEST_POINTS_ON_MESH_ARGTYPES.items():
+        getattr(L, name).argtypes = list(types)
     L.mmx_eval_jacobian_host.argtypes = [vp, vp, vp, vp, vp, i32]
     L.mmx_eval_skeleton_state_host.argtypes = [vp, vp, vp]
     L.mmx_debug_tree_normal_equations.argtypes = [vp, vp, vp, vp, vp]
@@ -307,6 +310,14 @@ def closest_points_plan(batch: int, num_source: int, num_target: int, with_norma
     return dict(sources_per_workgroup=s.value, target_tile=t.value, target_ways=w.value)
 
 
+def closest_points_on_mesh_plan(batch: int, num_source: int, num_triangles: int) -> dict:
+    """The launch decision of mmx_closest_points_on_mesh (mmx_closest_points_on_mesh_plan, no GPU needed):
+    dict(sources_per_workgroup, triangle_tile, triangle_ways)."""
+    s, t, w = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(lib().mmx_closest_points_on_mesh_plan(int(batch), int(num_source), int(num_triangles), C.byref(s), C.byref(t), C.byref(w)))
+    return dict(sources_per_workgroup=s.value, triangle_tile=t.value, triangle_ways=w.value)
+
+
 def closest_points(source, target, max_dist=float("inf"), source_normals=None, target_normals=None, min_normal_dot=0.0, want_dist2=True, want_points=True):
     """mmx_closest_points on torch device tensors, one kernel on the current stream: for every source point [B,N,3] the nearest
     eligible target point of the same instance (target [B,M,3], or [M,3] shared by the batch).  Eligible: a finite squared
@@ -455,7 +466,8 @@ class Skin:
 class Mesh:
     """A triangle mesh on a device (mmx_mesh): area-weighted vertex normals of posed vertices [B,V,3] and their backward
     pass.  triangles [T,3] integers (host or device; copied once), num_vertices V.  The counterpart of
-    pymomentum.geometry.compute_vertex_normals / Mesh::updateNormals; one kernel per call on the current stream."""
+    pymomentum.geometry.compute_vertex_normals / Mesh::updateNormals; one kernel per call on the current stream.
+    closest_points: the nearest point on the posed mesh for every source point (pymomentum.geometry.find_closest_points_on_mesh)."""
 
     def __init__(self, triangles, num_vertices: int, device: int = 0):
         import torch
@@ -519,6 +531,36 @@ class Mesh:
         self._f32(out, B, "out")
         _check(lib().mmx_vertex_normals_backward(self._h, B, _dev(positions), _dev(sums), _dev(grad_normals), _dev(out), _stream_ptr()))
         return out
+
+    def closest_points(self, source, vertices, max_dist=float("inf"), want_barycentric=True, want_points=True, want_dist2=False):
+        """mmx_closest_points_on_mesh on torch device tensors, one kernel on the current stream: for every source point [B,N,3]
+        the nearest point ON the nearest eligible triangle of the same instance's posed mesh (vertices [B,V,3], or [V,3] shared
+        by the batch).  Eligible: a triangle whose face vector is not three exact zeros and whose record is finite, at a finite
+        squared distance (the residual vector's, float32) <= max_dist^2.  Returns (face_index [B,N] int32 with -1 = none,
+        barycentric [B,N,3] = (w_a, w_b, w_c) or None, points [B,N,3] or None, dist2 [B,N] or None); zeros / +inf where none;
+        ties go to the lowest face index.  No autograd graph."""
+        import torch
+
+        def f32(t, what):
+            assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), what
+            return t
+
+        f32(source, "source")
+        assert source.dim() == 3 and source.shape[2] == 3 and source.shape[0] >= 1 and source.shape[1] >= 1, "source must be [B,N,3]"
+        B, N = int(source.shape[0]), int(source.shape[1])
+        f32(vertices, "vertices")
+        shared = vertices.dim() == 2
+        assert tuple(vertices.shape) == ((self.V, 3) if shared else (B, self.V, 3)), ("vertices must be [B,V,3] or [V,3]", tuple(vertices.shape))
+        assert source.device == self.device and vertices.device == self.device, "source / vertices are not on the mesh's device"
+        with torch.cuda.device(self.device):
+            face = torch.empty((B, N), dtype=torch.int32, device=self.device)
+            bary = torch.empty((B, N, 3), dtype=torch.float32, device=self.device) if want_barycentric else None
+            points = torch.empty((B, N, 3), dtype=torch.float32, device=self.device) if want_points else None
+            dist2 = torch.empty((B, N), dtype=torch.float32, device=self.device) if want_dist2 else None
+            _check(lib().mmx_closest_points_on_mesh(
+                self._h, B, N, _dev(source), _dev(vertices), int(shared), float(max_dist), _dev(face), _dev(bary), _dev(points), _dev(dist2),
+                _stream_ptr()))  # fmt: skip
+        return face, bary, points, dist2
 
 
 # Route every Problem created from here on starts with ("auto" | "fused" | "wide" | "explicit_jacobian" | "wave"): the parity tests

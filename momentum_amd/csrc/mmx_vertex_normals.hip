@@ -175,13 +175,18 @@ __global__ void __launch_bounds__(kMeshThreads) vertexNormalsBackwardKernel(
 } // namespace
 } // namespace mmx
 
-// A triangle mesh on a device (mmx_mesh_create): the uploaded incidence list of the vertex-normal kernels
+// A triangle mesh on a device (mmx_mesh_create): the uploaded incidence list of the vertex-normal kernels and the plain
+// triangle list [T][3] that mmx_closest_points_on_mesh.hip streams
 struct mmx_mesh {
   int32_t device = 0, V = 0, T = 0;
   void* records = nullptr;
   void* groups = nullptr; // groupBase [G] then groupMax [G]
+  void* triangles = nullptr; // [T][3]
   int32_t numGroups = 0;
   ~mmx_mesh() {
+    if (triangles != nullptr) {
+      (void)hipFree(triangles);
+    }
     if (records != nullptr) {
       (void)hipFree(records);
     }
@@ -200,6 +205,14 @@ struct mmx_mesh {
 };
 
 namespace mmx {
+// what mmx_closest_points_on_mesh.hip reads of a handle
+const int32_t* meshTriangleList(const mmx_mesh* mesh) {
+  return static_cast<const int32_t*>(mesh->triangles);
+}
+int32_t meshDeviceOrdinal(const mmx_mesh* mesh) {
+  return mesh->device;
+}
+
 namespace {
 
 int32_t hipFail(const char* fn, const char* what, hipError_t e) {
@@ -303,6 +316,9 @@ int32_t mmx_mesh_create(int32_t num_vertices, int32_t num_triangles, const int32
   const size_t recBytes = std::max<size_t>(t.records.size(), 4) * sizeof(int32_t), grpBytes = size_t(m->numGroups) * sizeof(int32_t);
   e = hipMalloc(&m->records, recBytes);
   e = e != hipSuccess ? e : hipMalloc(&m->groups, 2 * grpBytes);
+  const size_t triBytes = size_t(num_triangles) * 3 * sizeof(int32_t);
+  e = e != hipSuccess ? e : hipMalloc(&m->triangles, triBytes);
+  e = e != hipSuccess ? e : hipMemcpy(m->triangles, triangles, triBytes, hipMemcpyHostToDevice);
   if (e == hipSuccess && !t.records.empty()) {
     e = hipMemcpy(m->records, t.records.data(), t.records.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   }

@@ -3,7 +3,8 @@
 find_closest_points is the nearest-point step of an ICP loop (mmx_closest_points: one kernel on the current stream), which
 the reference runs on the CPU.  It composes with the mesh stages: the posed vertices of momentum_amd.autograd.skin_points go
 in as points_source without leaving the device.  compute_vertex_normals (mmx_vertex_normals, differentiable) makes the
-normals of those vertices that the overload with normals takes.
+normals of those vertices that the overload with normals takes.  find_closest_points_on_mesh is the point-to-SURFACE form
+(mmx_closest_points_on_mesh): the nearest point on the nearest triangle, with its face index and barycentric coordinates.
 """
 from __future__ import annotations
 
@@ -11,7 +12,7 @@ import math
 
 from . import capi
 
-__all__ = ["find_closest_points", "compute_vertex_normals"]
+__all__ = ["find_closest_points", "find_closest_points_on_mesh", "compute_vertex_normals"]
 
 
 def compute_vertex_normals(vertex_positions, triangles):
@@ -86,3 +87,47 @@ def find_closest_points(*args, max_dist: float = math.inf, min_normal_dot: float
     if single:
         return points[0], index[0], valid[0]
     return points, index, valid
+
+
+def find_closest_points_on_mesh(points_source, vertices_target, faces_target, *, max_dist: float = math.inf):
+    """For every source point the nearest point ON the posed triangle mesh of the same batch element, the call shape of
+    pymomentum.geometry.find_closest_points_on_mesh(points_source, vertices_target, faces_target).
+
+    points_source [B, N, 3] (or [N, 3]: one element; vertices_target is then [V, 3]), vertices_target [B, V, 3] or [V, 3]
+    (shared by the batch), float32 cuda tensors; faces_target a capi.Mesh (the loop form: the handle's triangle list is on
+    the device already and the call is one kernel) or an integer tensor / array [T, 3] (the convenience form: a handle is
+    built for the call).  max_dist is an extension of this library (keyword-only; inf reproduces a call without it).
+
+    A triangle with a repeated vertex (a face vector of exact zeros) or a non-finite vertex is never returned; among equally
+    near triangles the lowest face index wins; a non-finite source is invalid.  See include/mmx.h for the arithmetic.
+
+    Returns (valid [B, N] bool; closest_points [B, N, 3] float32, zeros where invalid; face_index [B, N] int32, -1 where
+    invalid; barycentric [B, N, 3] float32 = the weights of the face's corners in the face's own order, each >= 0, zeros
+    where invalid).
+
+    The results carry no autograd graph.  The differentiable closest point is the recombination in torch, on the valid rows
+    (faces the [T, 3] long tensor of the mesh, b the batch index of a row):
+
+        (barycentric[..., None] * vertices[b, faces[face_index]]).sum(-2)
+
+    whose gradient reaches all three vertices of each face (the weights are held fixed, as in point-to-plane ICP).
+    """
+    single = points_source.dim() == 2
+    src = (points_source.detach()[None] if single else points_source.detach()).contiguous()
+    vtx = vertices_target.detach().contiguous()
+    assert src.dim() == 3 and src.shape[2] == 3, "points_source must be [B, N, 3] or [N, 3]"
+    assert vtx.dim() in (2, 3) and vtx.shape[-1] == 3, "vertices_target must be [B, V, 3] or [V, 3]"
+    own = not isinstance(faces_target, capi.Mesh)
+    mesh = capi.Mesh(faces_target, int(vtx.shape[-2]), device=src.device.index or 0) if own else faces_target
+    try:
+        face, bary, points, _ = mesh.closest_points(src, vtx, float(max_dist), want_barycentric=True, want_points=True, want_dist2=False)
+    finally:
+        if own:
+            import torch
+
+            torch.cuda.current_stream(src.device).synchronize()  # (the kernel reads the handle's triangle list)
+            mesh.close()
+    valid = face >= 0
+    if single:
+        return valid[0], points[0], face[0], bary[0]
+    return valid, points, face, bary
