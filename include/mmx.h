@@ -1019,6 +1019,88 @@ int32_t mmx_host_skin_tables(
     int32_t* num_entries);
 
 /*
+ * Gauss-Newton terms of vertex constraints on a skinned mesh: H = J^T J, g = J^T (sigma f) and the error of a batch of
+ * constraints on a mmx_skin, over the problem's enabled parameters -- the counterpart of mmx_eval_normal_equations for the
+ * skin, in its layout, so that the two sets of terms add and a caller takes the step theta -= (H + lambda I)^-1 g with a
+ * batched Cholesky (the joint-constraint terms, limits and prior from mmx_eval_normal_equations added or not).  Nothing is
+ * solved here and mmx_solve does not read these terms.  Added without an ABI bump (no struct grows): a library that predates
+ * the functions lacks the symbols -- that is the feature probe.
+ *   meaning     with out [B][V][3] exactly what mmx_skin_points gives (rest_dev of the descriptor: the per-instance rest, as
+ *               there) on the state of mmx_eval_skeleton_state at theta, constraint c of instance b has the point
+ *                 x_c = sum_{i < S} barycentric[b][c][i] out[b][vertex[b][c][i]]         S = corners: 1 or 3
+ *               (S = 1: a mesh vertex, barycentric not read, weight 1; S = 3: a triangle's corners with barycentric weights,
+ *               what mmx_closest_points_on_mesh returns) and the rows
+ *                 MMX_VC_POSITION  f = x_c - target_c                three rows
+ *                 MMX_VC_PLANE     f = normal_c . (x_c - target_c)   one row; normal_c used as given, not normalised
+ *               scaled by sigma_c = sqrt(function_weight weight[b][c]); error = sum_c function_weight weight[b][c] |f|^2 --
+ *               the weighting of the joint-constraint blocks, with no further constant.
+ *   J           the exact derivative of the rows with respect to theta of the composed forward as this library defines it:
+ *               the local quaternions renormalised in double (as in mmx_eval_skeleton_state_backward), the skin's quaternion
+ *               used as the state holds it.  Row r of J is what mmx_eval_skeleton_state_backward(mmx_skin_points_backward(.))
+ *               returns for the cotangent of row r.
+ *   outputs     for the n enabled parameters, ascending -- the order and compaction of mmx_eval_normal_equations:
+ *                 jtj_dev [B][n][n] float  full and exactly symmetric      jtr_dev [B][n] float  same sign: a step is theta -= delta
+ *                 err_dev [B] double
+ *               Any may be NULL (not all three); an output has the same bits whichever others were requested.  Every entry is
+ *               written: an enabled parameter that moves no constrained vertex gets exact zeros.
+ *   skipped     a constraint contributes exact zeros when weight[b][c] is not > 0 (zero, negative, NaN) or any of its vertex
+ *               indices is negative (face_index = -1 of the closest-point kernels) or >= V; such an index is never
+ *               dereferenced and nothing else of the constraint is read.  Non-finite targets or normals behind a positive
+ *               weight are ordinary inputs: that instance's results are non-finite, no other's.
+ *   arrays      vertex [B][C][S] int32, NULL only with S = 1 and C = V (constraint c is vertex c); barycentric [B][C][S],
+ *               NULL when S = 1; target [B][C][3]; normal [B][C][3], MMX_VC_PLANE only; weight [B][C], NULL = every weight
+ *               1; rest [B][V][3] or NULL.  B is the problem's batch.
+ *   refusals    before any output is touched, with a message naming the condition: MMX_ERR_INVALID_ARGUMENT for a skin on
+ *               another rig, a null required pointer, all outputs null, count < 1, corners outside {1, 3}, an unknown type,
+ *               MMX_VC_PLANE without normals, a non-finite or negative function_weight; MMX_ERR_UNSUPPORTED for more than
+ *               MMX_SKIN_NE_MAX_SOLVED (128) enabled parameters -- the accumulators of the kernel's four waves -- or tables
+ *               beyond the kernel's LDS budget (160 KB).
+ *   determinism an instance's results depend on that instance's inputs only -- not on the batch size, its position in the
+ *               batch, or the run (no floating-point atomics; fixed summation order: rows ascending within an entry).
+ * One kernel is enqueued on `stream` and the call returns (no memset node, no stream wait, no host read, no device scratch);
+ * after one warm-up call (a kernel attribute is raised where the tables need more than 64 KB of LDS) it can be captured into a
+ * HIP graph.  The _host form takes host arrays in the descriptor and for theta and the outputs, copies in, runs, copies out
+ * and synchronises like the other host wrappers.
+ *
+ * PROVENANCE: this restates momentum's vertex error function (VertexErrorFunctionT, the Position and Plane constraint types)
+ * from memory of the reference, without a checkout at hand, so it carries no file:line citations yet.  To confirm against
+ * the reference: any constant factor on the weight (kPositionWeight / kPlaneWeight), and whether the plane normal is
+ * normalised on ingest.  The Normal and SymmetricNormal types, which rotate the normal with the mesh, are not built.
+ */
+#define MMX_VC_POSITION 0
+#define MMX_VC_PLANE 1
+#define MMX_SKIN_NE_MAX_SOLVED 128
+typedef struct mmx_vertex_constraints {
+  int32_t type;             /* MMX_VC_* */
+  int32_t count;            /* C >= 1 constraints per instance */
+  int32_t corners;          /* S: 1 or 3 */
+  float function_weight;    /* finite, >= 0 */
+  const int32_t* vertex;    /* [B][C][S] or NULL */
+  const float* barycentric; /* [B][C][S] or NULL */
+  const float* target;      /* [B][C][3] */
+  const float* normal;      /* [B][C][3] or NULL */
+  const float* weight;      /* [B][C] or NULL */
+  const float* rest;        /* [B][V][3] or NULL */
+} mmx_vertex_constraints;
+int32_t mmx_skin_normal_equations(
+    mmx_problem* problem,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* constraints /* DEVICE arrays */,
+    const float* theta_dev,
+    float* jtj_dev,
+    float* jtr_dev,
+    double* err_dev,
+    void* stream);
+int32_t mmx_skin_normal_equations_host(
+    mmx_problem* problem,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* constraints /* HOST arrays */,
+    const float* theta_host,
+    float* jtj_host,
+    float* jtr_host,
+    double* err_host);
+
+/*
  * Batched nearest-point queries: for every source point of every instance, the index of the nearest eligible target point
  * of the same instance (and, optionally, its squared distance and the point itself).  The counterpart of
  * pymomentum.geometry.find_closest_points and of its overload with normals, which run on the CPU; what an ICP loop does

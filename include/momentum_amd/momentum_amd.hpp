@@ -567,6 +567,12 @@ class BatchedSkeletonSolverFunction {
       e[i] = ps[i] ? 1 : 0;
     }
     check(mmx_problem_set_enabled(handle_.get(), e.data()));
+    numEnabled_ = size_t(std::count(e.begin(), e.end(), uint8_t(1)));
+    enabledSet_ = true;
+  }
+  // the enabled parameters: the size n of the systems mmx_eval_normal_equations and DeviceSkin::normalEquations return
+  size_t numEnabledParameters() const {
+    return enabledSet_ ? numEnabled_ : character_.numParameters();
   }
   // uploads the constraint payload if it changed
   void sync() {
@@ -737,6 +743,8 @@ class BatchedSkeletonSolverFunction {
   size_t fnCols_ = 0;
   float lossPos_[2] = {2.f, 1.f}, lossOri_[2] = {2.f, 1.f};
   bool dirty_ = true;
+  size_t numEnabled_ = 0;
+  bool enabledSet_ = false;
 };
 
 // GaussNewtonSolverT<float> for every element of the batch at once.
@@ -831,6 +839,28 @@ class BatchedSkeletonState {
   std::vector<SkeletonState> states_;
 };
 
+// Vertex constraints on a skinned mesh (DeviceSkin::normalEquations; momentum's vertex error function, Position and Plane types):
+// per batch element `count` constraints, each a mesh vertex (corners = 1) or a point of a triangle (corners = 3: the
+// triangle's vertices and barycentric weights, what DeviceMesh::closestPoints returns), pulled to `target` -- by all three
+// coordinates, or with `normal` given along that normal only (point-to-plane; the normal is used as given).
+struct VertexConstraints {
+  size_t corners = 1; // 1 or 3
+  float functionWeight = 1.f;
+  std::vector<int32_t> vertex; // [batch][count][corners]; empty with corners = 1: constraint c is vertex c
+  std::vector<float> barycentric; // [batch][count][3] with corners = 3
+  std::vector<float> target; // [batch][count][3]
+  std::vector<float> normal; // [batch][count][3]: plane constraints; empty: position constraints
+  std::vector<float> weight; // [batch][count]; empty: 1.  A weight that is not > 0 or a vertex outside [0, V) skips the constraint
+  std::vector<float> restPositions; // [batch][V][3] per-element rest vertices; empty: the skin's own
+};
+// H = J^T J [batch][n][n] (full, symmetric), g = J^T r [batch][n] and the error [batch] over the n enabled parameters, in the
+// layout of mmx_eval_normal_equations: a Gauss-Newton step is parameters[enabled] -= (H + lambda I)^-1 g
+struct VertexNormalEquations {
+  size_t n = 0;
+  std::vector<float> jtj, jtr;
+  std::vector<double> error;
+};
+
 // Linear-blend skinning on a device character (mmx_skin): momentum's SkinWeights (index / weight [V][K], K <= 8),
 // Character::inverseBindPose as 3 x 4 row-major affines [J][12] (empty = identity) and the mesh's rest vertices [V][3].
 // skinPoints: skeleton state [batch][numJoints][8] = (tx,ty,tz, qx,qy,qz,qw, s) -> posed vertices [batch][V][3] (applySSD for
@@ -899,6 +929,46 @@ class DeviceSkin {
       size_t batch, const float* state, const float* restPositions, const float* vertexGradient, float* stateGradient, float* restGradient,
       void* stream) const {
     check(mmx_skin_points_backward(handle_.get(), int32_t(batch), state, restPositions, vertexGradient, stateGradient, restGradient, stream));
+  }
+  // The Gauss-Newton terms of vertex constraints on this skin at modelParameters [batch][numParameters], over the function's
+  // enabled parameters (mmx_skin_normal_equations: one kernel; nothing is solved and the function's own constraints are not
+  // read).  `function` must be on the skin's character.  Throws for more than MMX_SKIN_NE_MAX_SOLVED enabled parameters.
+  VertexNormalEquations normalEquations(
+      const BatchedSkeletonSolverFunction& function, const std::vector<float>& modelParameters, const VertexConstraints& c) const {
+    const size_t batch = function.batchSize(), count = c.target.size() / (3 * (batch ? batch : 1));
+    if (modelParameters.size() != batch * function.getNumParameters()) {
+      throw std::runtime_error("momentum_amd: modelParameters.size() != batch * numParameters");
+    }
+    auto sized = [&](size_t have, size_t per, bool optional) { return (optional && have == 0) || have == batch * count * per; };
+    if (count == 0 || c.target.size() != batch * count * 3 || !sized(c.vertex.size(), c.corners, c.corners == 1) ||
+        !sized(c.barycentric.size(), 3, c.corners == 1) || !sized(c.normal.size(), 3, true) || !sized(c.weight.size(), 1, true) ||
+        (!c.restPositions.empty() && c.restPositions.size() != batch * numVertices_ * 3)) {
+      throw std::runtime_error("momentum_amd: vertex constraint arrays must be [batch][count][...] with one count");
+    }
+    mmx_vertex_constraints d{};
+    d.type = c.normal.empty() ? MMX_VC_POSITION : MMX_VC_PLANE;
+    d.count = int32_t(count);
+    d.corners = int32_t(c.corners);
+    d.function_weight = c.functionWeight;
+    d.vertex = c.vertex.empty() ? nullptr : c.vertex.data();
+    d.barycentric = c.barycentric.empty() ? nullptr : c.barycentric.data();
+    d.target = c.target.data();
+    d.normal = c.normal.empty() ? nullptr : c.normal.data();
+    d.weight = c.weight.empty() ? nullptr : c.weight.data();
+    d.rest = c.restPositions.empty() ? nullptr : c.restPositions.data();
+    VertexNormalEquations out;
+    out.n = function.numEnabledParameters();
+    out.jtj.resize(batch * out.n * out.n);
+    out.jtr.resize(batch * out.n);
+    out.error.resize(batch);
+    check(mmx_skin_normal_equations_host(function.handle(), handle_.get(), &d, modelParameters.data(), out.jtj.data(), out.jtr.data(), out.error.data()));
+    return out;
+  }
+  // device form: the descriptor's arrays, modelParameters and the outputs (any of them null, not all) are device memory
+  void normalEquations(
+      const BatchedSkeletonSolverFunction& function, const mmx_vertex_constraints& deviceArrays, const float* modelParameters, float* jtj,
+      float* jtr, double* error, void* stream) const {
+    check(mmx_skin_normal_equations(function.handle(), handle_.get(), &deviceArrays, modelParameters, jtj, jtr, error, stream));
   }
 
  private:

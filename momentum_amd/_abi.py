@@ -90,7 +90,33 @@ CLOSEST_POINTS_ON_MESH_ARGTYPES = {
     # (batch, num_source, num_triangles, &sources_per_workgroup, &triangle_tile, &triangle_ways)
     "mmx_closest_points_on_mesh_plan": (C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p),
 }  # fmt: skip
-MMX_LOSS_WELSCH = float(np.finfo(np.float32).min)  # GeneralizedLossT::kWelsch
+# vertex constraints on a skin (mmx_skin_normal_equations)
+MMX_VC_POSITION, MMX_VC_PLANE = 0, 1
+MMX_SKIN_NE_MAX_SOLVED = 128
+
+
+class VertexConstraints(C.Structure):
+    """mmx_vertex_constraints: the arrays of a batch of vertex constraints (device arrays, or host arrays for the _host form)."""
+
+    _fields_ = [
+        ("type", C.c_int32),
+        ("count", C.c_int32),
+        ("corners", C.c_int32),
+        ("function_weight", C.c_float),
+        ("vertex", C.c_void_p),
+        ("barycentric", C.c_void_p),
+        ("target", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("weight", C.c_void_p),
+        ("rest", C.c_void_p),
+    ]
+
+
+# (problem, skin, &constraints, theta, jtj, jtr, err, stream); the _host form: the same without the stream
+SKIN_NORMAL_EQUATIONS_ARGTYPES = (
+    C.c_void_p, C.c_void_p, C.POINTER(VertexConstraints), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+)  # fmt: skip
+MMX_LOSS_WELSCH =float(np.finfo(np.float32).min)  # GeneralizedLossT::kWelsch
 MMX_LIMIT_MINMAX = 0  # momentum::LimitType values (character/parameter_limits.h:20-31)
 MMX_LIMIT_MINMAX_JOINT = 1
 MMX_LIMIT_MINMAX_JOINT_PASSIVE = 2  # accepted and ignored, like LimitErrorFunctionT does

@@ -38,6 +38,7 @@ SYMBOLS = [
     "mmx_mesh_create", "mmx_mesh_destroy", "mmx_mesh_num_vertices", "mmx_mesh_num_triangles", "mmx_vertex_normals",
     "mmx_vertex_normals_backward", "mmx_vertex_normals_host", "mmx_vertex_normals_backward_host", "mmx_host_mesh_tables",
     "mmx_closest_points_on_mesh", "mmx_closest_points_on_mesh_host", "mmx_closest_points_on_mesh_plan",
+    "mmx_skin_normal_equations", "mmx_skin_normal_equations_host",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
     "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
@@ -123,6 +124,8 @@ def lib() -> C.CDLL:
     L.mmx_mesh_destroy.restype = None
     for name, types in _abi.CLOSEST_POINTS_ON_MESH_ARGTYPES.items():
         getattr(L, name).argtypes = list(types)
+    L.mmx_skin_normal_equations.argtypes = list(_abi.SKIN_NORMAL_EQUATIONS_ARGTYPES)
+    L.mmx_skin_normal_equations_host.argtypes = list(_abi.SKIN_NORMAL_EQUATIONS_ARGTYPES[:-1])
     L.mmx_eval_jacobian_host.argtypes = [vp, vp, vp, vp, vp, i32]
     L.mmx_eval_skeleton_state_host.argtypes = [vp, vp, vp]
     L.mmx_debug_tree_normal_equations.argtypes = [vp, vp, vp, vp, vp]
@@ -855,6 +858,54 @@ class Problem:
         jtr = torch.empty((self.B, self.n), dtype=torch.float32, device=self.device)
         err = torch.empty((self.B,), dtype=torch.float64, device=self.device)
         _check(lib().mmx_eval_normal_equations(self._h, _dev(theta), _dev(jtj), _dev(jtr), _dev(err), _stream_ptr()))
+        return jtj, jtr, err
+
+    def vertex_normal_equations(
+        self, skin, theta, target, *, vertex=None, barycentric=None, normal=None, weight=None, rest=None, function_weight=1.0,
+        want=("jtj", "jtr", "err"),
+    ):
+        """Gauss-Newton terms of vertex constraints on `skin` (mmx_skin_normal_equations): (jtj [B,n,n] float32, jtr [B,n]
+        float32, err [B] float64) over the enabled parameters in the layout of normal_equations, so that the two add and a
+        step is theta[:, enabled] -= cholesky_solve(jtj + lambda I, jtr).  An output not named in `want` is None.
+
+        target [B,C,3]; vertex None (constraint c is vertex c: C = V), [B,C] (vertices) or [B,C,3] (triangle corners, then
+        barycentric [B,C,3]: what Mesh.closest_points returns as faces[face_index] and barycentric); normal [B,C,3] makes the
+        constraints point-to-plane, n . (x - target), the normal used as given; weight [B,C] float or bool (a `valid` mask),
+        None = 1; rest [B,V,3] per-instance rest positions; a constraint whose weight is not > 0 or with an index outside
+        [0, V) contributes exact zeros.  float32 / int32 cuda tensors; one kernel on the current stream."""
+        import torch
+
+        theta = self._theta(theta)
+        B = self.B
+        f32 = lambda t, shape, what: skin._f32(t.contiguous() if t.dtype == torch.float32 else t.to(torch.float32).contiguous(), shape, what)
+        assert isinstance(target, torch.Tensor) and target.dim() == 3 and target.shape[0] == B and target.shape[2] == 3, "target must be [B,C,3]"
+        Cn = int(target.shape[1])
+        target = f32(target, (B, Cn, 3), "target")
+        S = 1
+        if vertex is not None:
+            assert isinstance(vertex, torch.Tensor) and vertex.is_cuda and vertex.dim() in (2, 3), "vertex must be [B,C] or [B,C,3]"
+            S = 1 if vertex.dim() == 2 else int(vertex.shape[2])
+            vertex = vertex.to(torch.int32).contiguous()
+            assert tuple(vertex.shape[:2]) == (B, Cn), (tuple(vertex.shape), (B, Cn))
+        if barycentric is not None:
+            barycentric = f32(barycentric, (B, Cn, S), "barycentric")
+        if normal is not None:
+            normal = f32(normal, (B, Cn, 3), "normal")
+        if weight is not None:
+            weight = f32(weight, (B, Cn), "weight")
+        if rest is not None:
+            rest = f32(rest, (B, skin.V, 3), "rest")
+        unknown = set(want) - {"jtj", "jtr", "err"}
+        assert not unknown, f"unknown outputs {sorted(unknown)}"
+        n = self.n
+        jtj = torch.empty((B, n, n), dtype=torch.float32, device=self.device) if "jtj" in want else None
+        jtr = torch.empty((B, n), dtype=torch.float32, device=self.device) if "jtr" in want else None
+        err = torch.empty((B,), dtype=torch.float64, device=self.device) if "err" in want else None
+        d = _abi.VertexConstraints(
+            _abi.MMX_VC_PLANE if normal is not None else _abi.MMX_VC_POSITION, Cn, S, float(function_weight),
+            *(None if t is None else t.data_ptr() for t in (vertex, barycentric, target, normal, weight, rest)),
+        )  # fmt: skip
+        _check(lib().mmx_skin_normal_equations(self._h, skin._h, C.byref(d), _dev(theta), _dev(jtj), _dev(jtr), _dev(err), _stream_ptr()))
         return jtj, jtr, err
 
     def jtj_history(self, theta_init, parameter_history, iterations, regularization, out=None):

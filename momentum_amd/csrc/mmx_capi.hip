@@ -27,6 +27,7 @@
 #include "mmx_kernels.hpp"
 #include "mmx_skin_tables.hpp"
 #include "mmx_solve_plan.hpp"
+#include "mmx_vertex_constraints.hpp"
 
 namespace {
 
@@ -238,6 +239,7 @@ struct mmx_skin {
   DevBuf dJoint, dWeight, dInverseBind, dRest, dJointStart, dEntryVertex, dEntryWeight, dWaveStart;
   mmx::SkinDev dev{};
   DevBuf sState, sRest, sOut, sStateGrad, sRestGrad;
+  DevBuf sVcVertex, sVcBary, sVcTarget, sVcNormal, sVcWeight, sVcTheta, sVcJtj, sVcJtr, sVcErr; // mmx_skin_normal_equations_host
 };
 
 struct mmx_problem {
@@ -2727,6 +2729,120 @@ int32_t mmx_skin_points_backward_host(
   MMX_HIP(hipMemcpy(state_grad_host, skin->sStateGrad.p, nState, hipMemcpyDeviceToHost));
   if (rest_grad_host != nullptr) {
     MMX_HIP(hipMemcpy(rest_grad_host, skin->sRestGrad.p, nVert, hipMemcpyDeviceToHost));
+  }
+  return MMX_OK;
+}
+
+// ---- Gauss-Newton terms of vertex constraints on a skin (mmx_skin_normal_equations.hip; intake: mmx_vertex_constraints.cpp)
+int32_t mmx_skin_normal_equations(
+    mmx_problem* pb,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* c,
+    const float* theta_dev,
+    float* jtj_dev,
+    float* jtr_dev,
+    double* err_dev,
+    void* stream) {
+  MMX_ZONE("mmx_skin_normal_equations (vertex constraints: JtJ, JtR, error)");
+  MMX_TRY(checkProblem(pb, false));
+  if (skin == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_normal_equations: skin handle is null");
+  }
+  const mmx::ProblemDev& d = pb->dev;
+  const int32_t nsrc = int32_t(pb->tables.colSources.size());
+  mmx::VertexConstraintsFacts f;
+  f.sameRig = skin->rig == pb->rig;
+  f.haveTheta = theta_dev != nullptr;
+  f.haveOutput = jtj_dev != nullptr || jtr_dev != nullptr || err_dev != nullptr;
+  f.skinVertices = skin->dev.V;
+  f.solved = d.n;
+  if (c != nullptr && (c->corners == 1 || c->corners == 3) && d.n >= 1 && d.n <= mmx::kSkinNeMaxSolved) {
+    f.ldsBytes = mmx::skinNormalEquationsLdsBytes(pb->rig->J, pb->rig->P, d.n, nsrc, c->corners, skin->dev.K);
+  }
+  std::string err;
+  const int32_t rc = mmx::checkVertexConstraints(c, f, err);
+  if (rc != MMX_OK) {
+    return fail(rc, "mmx_skin_normal_equations: " + err);
+  }
+  mmx::SkinNeColumnsDev cols{};
+  cols.n = d.n, cols.nsrc = nsrc;
+  cols.enabledList = d.enabledList, cols.colStart = d.colStart, cols.colSources = d.colSources, cols.jointTin = d.jointTin;
+  mmx::VertexConstraintsDev vc{};
+  vc.type = c->type, vc.C = c->count, vc.S = c->corners, vc.fw = c->function_weight;
+  vc.vertex = c->vertex, vc.bary = c->corners == 3 ? c->barycentric : nullptr, vc.target = c->target;
+  vc.normal = c->type == MMX_VC_PLANE ? c->normal : nullptr, vc.weight = c->weight, vc.rest = c->rest;
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  MMX_HIP(mmx::launchSkinNormalEquations(pb->rigDev, cols, skin->dev, vc, pb->B, theta_dev, jtj_dev, jtr_dev, err_dev, static_cast<hipStream_t>(stream)));
+  return MMX_OK;
+}
+
+int32_t mmx_skin_normal_equations_host(
+    mmx_problem* pb,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* c,
+    const float* theta_host,
+    float* jtj_host,
+    float* jtr_host,
+    double* err_host) {
+  MMX_ZONE("mmx_skin_normal_equations_host");
+  MMX_TRY(checkProblem(pb, false));
+  if (skin == nullptr || c == nullptr || theta_host == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_normal_equations_host: skin / constraints / theta is null");
+  }
+  if (c->count < 1 || (c->corners != 1 && c->corners != 3)) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_normal_equations_host: count must be >= 1 and corners 1 or 3");
+  }
+  const size_t B = size_t(pb->B), P = size_t(pb->rig->P), n = size_t(pb->dev.n), C = size_t(c->count), S = size_t(c->corners);
+  const size_t V = size_t(skin->dev.V);
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  mmx_vertex_constraints dv = *c;
+  auto stage = [&](DevBuf& buf, const void* src, size_t bytes, const void** out) -> hipError_t {
+    *out = nullptr;
+    if (src == nullptr) {
+      return hipSuccess;
+    }
+    hipError_t e = buf.ensure(bytes);
+    if (e != hipSuccess) {
+      return e;
+    }
+    *out = buf.p;
+    return hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice);
+  };
+  const void* q = nullptr;
+  MMX_HIP(stage(skin->sVcVertex, c->vertex, B * C * S * sizeof(int32_t), &q));
+  dv.vertex = static_cast<const int32_t*>(q);
+  MMX_HIP(stage(skin->sVcBary, c->barycentric, B * C * S * sizeof(float), &q));
+  dv.barycentric = static_cast<const float*>(q);
+  MMX_HIP(stage(skin->sVcTarget, c->target, B * C * 3 * sizeof(float), &q));
+  dv.target = static_cast<const float*>(q);
+  MMX_HIP(stage(skin->sVcNormal, c->normal, B * C * 3 * sizeof(float), &q));
+  dv.normal = static_cast<const float*>(q);
+  MMX_HIP(stage(skin->sVcWeight, c->weight, B * C * sizeof(float), &q));
+  dv.weight = static_cast<const float*>(q);
+  MMX_HIP(stage(skin->sRest, c->rest, B * V * 3 * sizeof(float), &q));
+  dv.rest = static_cast<const float*>(q);
+  MMX_HIP(stage(skin->sVcTheta, theta_host, B * P * sizeof(float), &q));
+  if (jtj_host != nullptr) {
+    MMX_HIP(skin->sVcJtj.ensure(B * n * n * sizeof(float)));
+  }
+  if (jtr_host != nullptr) {
+    MMX_HIP(skin->sVcJtr.ensure(B * n * sizeof(float)));
+  }
+  if (err_host != nullptr) {
+    MMX_HIP(skin->sVcErr.ensure(B * sizeof(double)));
+  }
+  MMX_TRY(mmx_skin_normal_equations(
+      pb, skin, &dv, skin->sVcTheta.as<float>(), jtj_host ? skin->sVcJtj.as<float>() : nullptr, jtr_host ? skin->sVcJtr.as<float>() : nullptr,
+      err_host ? skin->sVcErr.as<double>() : nullptr, nullptr));
+  MMX_HIP(hipDeviceSynchronize());
+  if (jtj_host != nullptr) {
+    MMX_HIP(hipMemcpy(jtj_host, skin->sVcJtj.p, B * n * n * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  if (jtr_host != nullptr) {
+    MMX_HIP(hipMemcpy(jtr_host, skin->sVcJtr.p, B * n * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  if (err_host != nullptr) {
+    MMX_HIP(hipMemcpy(err_host, skin->sVcErr.p, B * sizeof(double), hipMemcpyDeviceToHost));
   }
   return MMX_OK;
 }

@@ -251,6 +251,31 @@ hipError_t launchSkinPoints(const SkinDev& sk, int B, const float* state, const 
 hipError_t launchSkinRestGrad(const SkinDev& sk, int B, const float* state, const float* outGrad, float* restGrad, hipStream_t stream);
 hipError_t launchSkinPointsBackward(
     const SkinDev& sk, int B, const float* state, const float* restInst, const float* outGrad, float* stateGrad, hipStream_t stream);
+// mmx_skin_normal_equations (mmx_skin_normal_equations.hip): H = J^T J, g = J^T (sigma f) and the error of a batch of vertex
+// constraints on a skin, over the problem's enabled parameters in enabledList order; one 256-thread workgroup per instance,
+// one kernel node.  Any of H / g / err may be null (not all).  n <= kSkinNeMaxSolved: the accumulators of the four waves.
+constexpr int kSkinNeMaxSolved = 128;
+struct SkinNeColumnsDev { // the problem's column tables (ProblemDev's) and the joints' DFS positions
+  int32_t n, nsrc; // enabled parameters; entries of colSources (disabled columns are empty)
+  const int32_t* enabledList; // [n]
+  const int32_t* colStart; // [P + 1]
+  const ColumnSourceDev* colSources; // [nsrc]
+  const int32_t* jointTin; // [J]
+};
+struct VertexConstraintsDev { // == mmx_vertex_constraints with device pointers
+  int32_t type, C, S;
+  float fw;
+  const int32_t* vertex; // [B][C][S] or null (S == 1, C == V: constraint c is vertex c)
+  const float* bary; // [B][C][S] or null (S == 1)
+  const float* target; // [B][C][3]
+  const float* normal; // [B][C][3] (MMX_VC_PLANE) or null
+  const float* weight; // [B][C] or null (every weight 1)
+  const float* rest; // [B][V][3] or null (the skin's rest positions)
+};
+size_t skinNormalEquationsLdsBytes(int J, int P, int n, int nsrc, int S, int K);
+hipError_t launchSkinNormalEquations(
+    const RigDev& rig, const SkinNeColumnsDev& cols, const SkinDev& sk, const VertexConstraintsDev& vc, int B, const float* theta, float* H,
+    float* g, double* err, hipStream_t stream);
 int fusedBlocksFor(int n); // number of 16-wide blocks the fused kernel is instantiated for, or -1
 hipError_t launchFusedSolve(
     const RigDev& rig,

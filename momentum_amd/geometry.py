@@ -5,6 +5,8 @@ the reference runs on the CPU.  It composes with the mesh stages: the posed vert
 in as points_source without leaving the device.  compute_vertex_normals (mmx_vertex_normals, differentiable) makes the
 normals of those vertices that the overload with normals takes.  find_closest_points_on_mesh is the point-to-SURFACE form
 (mmx_closest_points_on_mesh): the nearest point on the nearest triangle, with its face index and barycentric coordinates.
+vertex_normal_equations (mmx_skin_normal_equations) turns such correspondences into the Gauss-Newton terms H = J^T J and
+g = J^T r of the skinned mesh over the problem's parameters.
 """
 from __future__ import annotations
 
@@ -12,7 +14,7 @@ import math
 
 from . import capi
 
-__all__ = ["find_closest_points", "find_closest_points_on_mesh", "compute_vertex_normals"]
+__all__ = ["find_closest_points", "find_closest_points_on_mesh", "compute_vertex_normals", "vertex_normal_equations"]
 
 
 def compute_vertex_normals(vertex_positions, triangles):
@@ -131,3 +133,32 @@ def find_closest_points_on_mesh(points_source, vertices_target, faces_target, *,
     if single:
         return valid[0], points[0], face[0], bary[0]
     return valid, points, face, bary
+
+
+def vertex_normal_equations(
+    problem, skin, theta, target, *, vertex=None, barycentric=None, normal=None, weight=None, rest=None, function_weight=1.0,
+    want=("jtj", "jtr", "err"),
+):
+    """Gauss-Newton terms of vertex constraints on a skinned mesh: capi.Problem.vertex_normal_equations with the outputs of
+    the closest-point queries taken as they come.
+
+    problem a capi.Problem, skin a capi.Skin on its rig, theta [B, P]; target [B, C, 3] the points the constrained mesh points
+    are pulled to.  vertex: None (constraint c is vertex c), vertex indices [B, C], or corner triples [B, C, 3] -- e.g.
+    faces[face_index.long()] of find_closest_points_on_mesh, whose -1 rows may stay as they are: an index outside [0, V) in
+    any corner skips the constraint -- with barycentric [B, C, 3].  normal [B, C, 3]: point-to-plane rows n . (x - target), the
+    normal used as given.  weight [B, C]: floats, or a bool mask such as `valid` (False = skipped).
+
+    Returns (jtj [B, n, n], jtr [B, n], err [B] float64) over the enabled parameters, in the layout of
+    problem.normal_equations: the two sets of terms add.  The results carry no autograd graph.
+    """
+    import torch
+
+    prep = lambda t: None if t is None else t.detach()
+    if vertex is not None and vertex.dtype != torch.int32:
+        vertex = vertex.to(torch.int32)
+    if weight is not None and weight.dtype != torch.float32:
+        weight = weight.to(torch.float32)
+    return problem.vertex_normal_equations(
+        skin, theta.detach().contiguous(), prep(target), vertex=prep(vertex), barycentric=prep(barycentric), normal=prep(normal),
+        weight=prep(weight), rest=prep(rest), function_weight=function_weight, want=want,
+    )  # fmt: skip
