@@ -1101,6 +1101,99 @@ int32_t mmx_skin_normal_equations_host(
     double* err_host);
 
 /*
+ * The same terms with every instance's 32-row tiles divided over `parts` workgroups: for the shape a mesh fit has -- one
+ * scan or a short clip against a dense mesh -- where one workgroup per instance leaves the device idle.  Added without an ABI
+ * bump: the new symbols are the feature probe.  mmx_skin_normal_equations itself, its results and its defaults do not change.
+ *   meaning     everything mmx_skin_normal_equations documents (rows, sigma, J, skipped constraints, layout, sign) holds
+ *               unchanged.  With rows = C (MMX_VC_PLANE) or 3 C (MMX_VC_POSITION), T = ceil(rows / 32) tiles and
+ *               Pe = min(parts, T), part p owns the tiles [floor(p T / Pe), floor((p + 1) T / Pe)) -- no part is empty.  Tile
+ *               composition is that of the unsplit kernel (it depends on C, S and the type only); a position constraint
+ *               that straddles a part boundary is evaluated in both parts and writes the rows that fall in each.  Part p
+ *               produces the float32 matrix-core accumulators of the lower block triangle over its tiles (tiles ascending,
+ *               from zero), per column the double h0 + h1 of the unsplit kernel's g reduction over its tiles, and its 32
+ *               row threads' double error sums added in row order.  A second kernel writes, for every entry,
+ *                 H = float(sum_p double(acc_p))     g = float(sum_p g_p)     err = sum_p err_p
+ *               each sum over p ascending, in double, rounded once; H is mirrored as in the unsplit kernel, so it is
+ *               bitwise symmetric.  Every entry of every requested output is written; an output's bits do not depend on
+ *               which others were requested.
+ *   parts       1..MMX_SKIN_NE_MAX_PARTS, or 0 = the value mmx_skin_normal_equations_auto_parts reports.  An effective
+ *               parts of 1 (parts = 1, or T = 1) IS mmx_skin_normal_equations: its bits, one kernel node, the workspace
+ *               neither needed nor touched.  parts >= T gives the bits of parts = T.
+ *   workspace   device memory of at least mmx_skin_normal_equations_workspace_bytes(B, n, parts) bytes (n = the enabled
+ *               parameters; the size is taken for the parts asked for -- for parts = 0 the value it resolves to -- not for
+ *               Pe), 16-byte aligned; may be NULL / 0 when the effective parts is 1.  It is written before it is read:
+ *               its prior contents never reach a result, and it holds nothing a later call needs.
+ *   refusals    before any output or the workspace is touched, with a message naming the condition: every refusal of
+ *               mmx_skin_normal_equations, in its order, first; then MMX_ERR_INVALID_ARGUMENT for parts < 0 or
+ *               parts > MMX_SKIN_NE_MAX_PARTS, for a null workspace or workspace_bytes below the size above when Pe > 1,
+ *               and for a workspace that is not 16-byte aligned.  The _host form stages its arrays first and then
+ *               refuses in the same order.
+ *   determinism an instance's results depend on that instance's inputs and on Pe only -- not on the batch size, its
+ *               position in the batch, or the run (no atomics, no inter-workgroup synchronisation; the parts are added in a
+ *               fixed order).  Different Pe give results that differ in the last bits (the association of the sums).
+ *               parts = 0 therefore depends on the batch size, through the plan only: a caller who wants identical bits
+ *               across batch sizes pins `parts`.
+ *   plan        mmx_skin_normal_equations_plan (pure host, no device touched):
+ *                 parts = max(1, min(floor(compute_units workgroups_per_cu / batch), T, MMX_SKIN_NE_MAX_PARTS))
+ *               -- the device's workgroup slots per instance, as far as the tiles reach.  Every part repeats the set-up
+ *               (forward kinematics, posed affines, column sources), yet a part of a single tile was the fastest choice
+ *               at every measured shape; only humanoid72 p128 was measured.  MMX_ERR_INVALID_ARGUMENT, nothing written, for batch < 1, count < 1, an unknown type,
+ *               compute_units < 1 or workgroups_per_cu < 1.  mmx_skin_normal_equations_auto_parts feeds it the device's
+ *               compute-unit count and workgroups_per_cu = 2 where two workgroups' LDS fit in 160 KB, else 1; it refuses what
+ *               mmx_skin_normal_equations refuses of the problem, skin and descriptor's type, count and corners (the
+ *               arrays are not read and may be NULL).
+ * Two kernels are enqueued on `stream` (one when the effective parts is 1) and the call returns: no memset node, no stream
+ * wait, no host read; after one warm-up call it can be captured into a HIP graph as a linear chain of two kernel nodes.
+ * The _host form takes host arrays like mmx_skin_normal_equations_host and allocates and frees its own workspace.
+ */
+#define MMX_SKIN_NE_MAX_PARTS 512 /* 256 CUs x two workgroups per CU at one instance */
+int32_t mmx_skin_normal_equations_split(
+    mmx_problem* problem,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* constraints /* DEVICE arrays */,
+    const float* theta_dev,
+    float* jtj_dev,
+    float* jtr_dev,
+    double* err_dev,
+    int32_t parts,
+    void* workspace_dev,
+    int64_t workspace_bytes,
+    void* stream);
+int32_t mmx_skin_normal_equations_split_host(
+    mmx_problem* problem,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* constraints /* HOST arrays */,
+    const float* theta_host,
+    float* jtj_host,
+    float* jtr_host,
+    double* err_host,
+    int32_t parts);
+/* pure host: bytes a call needs; 0 for parts <= 1; -1 for batch < 1, num_enabled outside 1..128 or parts outside 0..512 */
+int64_t mmx_skin_normal_equations_workspace_bytes(int32_t batch, int32_t num_enabled, int32_t parts);
+int32_t mmx_skin_normal_equations_plan(
+    int32_t batch,
+    int32_t type,
+    int32_t count,
+    int32_t compute_units,
+    int32_t workgroups_per_cu,
+    int32_t* parts_out);
+int32_t mmx_skin_normal_equations_auto_parts(
+    mmx_problem* problem,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* constraints,
+    int32_t* parts_out);
+/* pure host: the tiles [*begin_out, *end_out) that part `part` of a call with `parts` parts over `tiles` tiles owns, and
+ * *effective_parts_out = min(parts, tiles) (any output may be NULL); MMX_ERR_INVALID_ARGUMENT, nothing written, for tiles < 1,
+ * parts outside 1..MMX_SKIN_NE_MAX_PARTS or part outside [0, min(parts, tiles)) */
+int32_t mmx_skin_normal_equations_part_range(
+    int32_t tiles,
+    int32_t parts,
+    int32_t part,
+    int32_t* begin_out,
+    int32_t* end_out,
+    int32_t* effective_parts_out);
+
+/*
  * Batched nearest-point queries: for every source point of every instance, the index of the nearest eligible target point
  * of the same instance (and, optionally, its squared distance and the point itself).  The counterpart of
  * pymomentum.geometry.find_closest_points and of its overload with normals, which run on the CPU; what an ICP loop does

@@ -935,6 +935,45 @@ class DeviceSkin {
   // read).  `function` must be on the skin's character.  Throws for more than MMX_SKIN_NE_MAX_SOLVED enabled parameters.
   VertexNormalEquations normalEquations(
       const BatchedSkeletonSolverFunction& function, const std::vector<float>& modelParameters, const VertexConstraints& c) const {
+    return normalEquationsHost(function, modelParameters, c, -1);
+  }
+  // ... with every instance's tiles divided over `parts` workgroups (mmx_skin_normal_equations_split_host: 1..
+  // MMX_SKIN_NE_MAX_PARTS, or 0 for the library's plan; for few instances against a dense mesh).  parts = 1 gives the bits of
+  // the form above; an instance's bits depend on its inputs and min(parts, tiles) only.
+  VertexNormalEquations normalEquations(
+      const BatchedSkeletonSolverFunction& function, const std::vector<float>& modelParameters, const VertexConstraints& c, int32_t parts) const {
+    if (parts < 0) {
+      throw std::runtime_error("momentum_amd: parts must be >= 0");
+    }
+    return normalEquationsHost(function, modelParameters, c, parts);
+  }
+  // device form: the descriptor's arrays, modelParameters and the outputs (any of them null, not all) are device memory
+  void normalEquations(
+      const BatchedSkeletonSolverFunction& function, const mmx_vertex_constraints& deviceArrays, const float* modelParameters, float* jtj,
+      float* jtr, double* error, void* stream) const {
+    check(mmx_skin_normal_equations(function.handle(), handle_.get(), &deviceArrays, modelParameters, jtj, jtr, error, stream));
+  }
+  // ... split: `workspace` is device memory of normalEquationsWorkspaceBytes(function, parts) bytes, 16-byte aligned (may be
+  // null when the effective parts is 1); two kernels on `stream`
+  void normalEquations(
+      const BatchedSkeletonSolverFunction& function, const mmx_vertex_constraints& deviceArrays, const float* modelParameters, float* jtj,
+      float* jtr, double* error, int32_t parts, void* workspace, int64_t workspaceBytes, void* stream) const {
+    check(mmx_skin_normal_equations_split(
+        function.handle(), handle_.get(), &deviceArrays, modelParameters, jtj, jtr, error, parts, workspace, workspaceBytes, stream));
+  }
+  // what parts = 0 resolves to for this function, skin and descriptor (type, count and corners are read, the arrays are not)
+  int32_t normalEquationsAutoParts(const BatchedSkeletonSolverFunction& function, const mmx_vertex_constraints& descriptor) const {
+    int32_t parts = 0;
+    check(mmx_skin_normal_equations_auto_parts(function.handle(), handle_.get(), &descriptor, &parts));
+    return parts;
+  }
+  static int64_t normalEquationsWorkspaceBytes(const BatchedSkeletonSolverFunction& function, int32_t parts) {
+    return mmx_skin_normal_equations_workspace_bytes(int32_t(function.batchSize()), int32_t(function.numEnabledParameters()), parts);
+  }
+
+ private:
+  VertexNormalEquations normalEquationsHost(
+      const BatchedSkeletonSolverFunction& function, const std::vector<float>& modelParameters, const VertexConstraints& c, int32_t parts) const {
     const size_t batch = function.batchSize(), count = c.target.size() / (3 * (batch ? batch : 1));
     if (modelParameters.size() != batch * function.getNumParameters()) {
       throw std::runtime_error("momentum_amd: modelParameters.size() != batch * numParameters");
@@ -961,17 +1000,14 @@ class DeviceSkin {
     out.jtj.resize(batch * out.n * out.n);
     out.jtr.resize(batch * out.n);
     out.error.resize(batch);
-    check(mmx_skin_normal_equations_host(function.handle(), handle_.get(), &d, modelParameters.data(), out.jtj.data(), out.jtr.data(), out.error.data()));
+    if (parts < 0) {
+      check(mmx_skin_normal_equations_host(function.handle(), handle_.get(), &d, modelParameters.data(), out.jtj.data(), out.jtr.data(), out.error.data()));
+    } else {
+      check(mmx_skin_normal_equations_split_host(
+          function.handle(), handle_.get(), &d, modelParameters.data(), out.jtj.data(), out.jtr.data(), out.error.data(), parts));
+    }
     return out;
   }
-  // device form: the descriptor's arrays, modelParameters and the outputs (any of them null, not all) are device memory
-  void normalEquations(
-      const BatchedSkeletonSolverFunction& function, const mmx_vertex_constraints& deviceArrays, const float* modelParameters, float* jtj,
-      float* jtr, double* error, void* stream) const {
-    check(mmx_skin_normal_equations(function.handle(), handle_.get(), &deviceArrays, modelParameters, jtj, jtr, error, stream));
-  }
-
- private:
   void checkSizes(size_t batch, const std::vector<float>& state, const std::vector<float>& restPositions) const {
     if (batch == 0 || state.size() != batch * character_.numJoints() * 8) {
       throw std::runtime_error("momentum_amd: state.size() != batch * numJoints * 8");

@@ -116,6 +116,22 @@ class VertexConstraints(C.Structure):
 SKIN_NORMAL_EQUATIONS_ARGTYPES = (
     C.c_void_p, C.c_void_p, C.POINTER(VertexConstraints), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
 )  # fmt: skip
+# the split form (an instance's tiles over several workgroups): name -> argument types, in the header's order
+MMX_SKIN_NE_MAX_PARTS = 512
+SKIN_NORMAL_EQUATIONS_SPLIT_ARGTYPES = {
+    # (problem, skin, &constraints, theta, jtj, jtr, err, parts, workspace, workspace_bytes, stream)
+    "mmx_skin_normal_equations_split": SKIN_NORMAL_EQUATIONS_ARGTYPES[:-1] + (C.c_int32, C.c_void_p, C.c_int64, C.c_void_p),
+    # (problem, skin, &constraints, theta, jtj, jtr, err, parts)
+    "mmx_skin_normal_equations_split_host": SKIN_NORMAL_EQUATIONS_ARGTYPES[:-1] + (C.c_int32,),
+    # (batch, num_enabled, parts) -> int64
+    "mmx_skin_normal_equations_workspace_bytes": (C.c_int32, C.c_int32, C.c_int32),
+    # (batch, type, count, compute_units, workgroups_per_cu, &parts)
+    "mmx_skin_normal_equations_plan": (C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p),
+    # (problem, skin, &constraints, &parts)
+    "mmx_skin_normal_equations_auto_parts": (C.c_void_p, C.c_void_p, C.POINTER(VertexConstraints), c_int32_p),
+    # (tiles, parts, part, &begin, &end, &effective_parts)
+    "mmx_skin_normal_equations_part_range": (C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p),
+}
 MMX_LOSS_WELSCH =float(np.finfo(np.float32).min)  # GeneralizedLossT::kWelsch
 MMX_LIMIT_MINMAX = 0  # momentum::LimitType values (character/parameter_limits.h:20-31)
 MMX_LIMIT_MINMAX_JOINT = 1

@@ -17,7 +17,7 @@ VARIANT = os.environ.get("MMX_BUILD_VARIANT", "")
 # ... and MMX_BUILD_FLAGS="..." appends compiler flags to such a variant build (e.g. -mllvm -amdgpu-sched-strategy=max-ilp)
 VARIANT_FLAGS = os.environ.get("MMX_BUILD_FLAGS", "").split() if VARIANT else []
 LIB = os.path.join(HERE, f"libmmx_hip_{VARIANT}.so" if VARIANT else "libmmx_hip.so")
-SOURCES = ["mmx_kernels.hip", "mmx_fused.hip", "mmx_capi.hip", "mmx_comm.hip", "mmx_f64.hip", "mmx_host_tables.cpp", "mmx_solve_plan.cpp", "mmx_constraint_intake.cpp", "mmx_wave.hip", "mmx_wave_frames.hip", "mmx_gradient.hip", "mmx_state_backward.hip", "mmx_skinning.hip", "mmx_skin_tables.cpp", "mmx_closest_points.hip", "mmx_closest_points_plan.cpp", "mmx_vertex_normals.hip", "mmx_mesh_tables.cpp", "mmx_closest_points_on_mesh.hip", "mmx_closest_points_on_mesh_plan.cpp", "mmx_skin_normal_equations.hip", "mmx_vertex_constraints.cpp"]
+SOURCES = ["mmx_kernels.hip", "mmx_fused.hip", "mmx_capi.hip", "mmx_comm.hip", "mmx_f64.hip", "mmx_host_tables.cpp", "mmx_solve_plan.cpp", "mmx_constraint_intake.cpp", "mmx_wave.hip", "mmx_wave_frames.hip", "mmx_gradient.hip", "mmx_state_backward.hip", "mmx_skinning.hip", "mmx_skin_tables.cpp", "mmx_closest_points.hip", "mmx_closest_points_plan.cpp", "mmx_vertex_normals.hip", "mmx_mesh_tables.cpp", "mmx_closest_points_on_mesh.hip", "mmx_closest_points_on_mesh_plan.cpp", "mmx_skin_normal_equations.hip", "mmx_vertex_constraints.cpp", "mmx_skin_normal_equations_plan.cpp"]
 FUSED_GROUPS = 7  # mmx_fused.hip is compiled once per group of template instantiations, in parallel (4: the wide route's tree kernels; 5, 6: the mixed-precision instantiations)
 # The solve kernels (one-launch solve, double solve) are compiled WITHOUT the machine-level loop-invariant code motion and
 # WITHOUT loop strength reduction: at their register budgets the per-lane address arithmetic the first hoists out of the
@@ -82,7 +82,7 @@ def build_info() -> dict:
         return {}
 # sources that include another source: their objects are rebuilt when that one changes
 SOURCE_DEPS = {"mmx_wave_frames.hip": ["mmx_wave.hip"]}
-HEADERS = ["mmx_device.hpp", "mmx_kernels.hpp", "mmx_tree.hpp", "mmx_fused_helpers.hpp", "mmx_mixed.hpp", "mmx_solver_rules.hpp", "mmx_host_tables.hpp", "mmx_solve_plan.hpp", "mmx_constraint_intake.hpp", "mmx_skin_tables.hpp", "mmx_closest_points_plan.hpp", "mmx_mesh_tables.hpp", "mmx_closest_points_on_mesh_plan.hpp", "mmx_vertex_constraints.hpp", os.path.join("..", "..", "include", "mmx.h")]
+HEADERS = ["mmx_device.hpp", "mmx_kernels.hpp", "mmx_tree.hpp", "mmx_fused_helpers.hpp", "mmx_mixed.hpp", "mmx_solver_rules.hpp", "mmx_host_tables.hpp", "mmx_solve_plan.hpp", "mmx_constraint_intake.hpp", "mmx_skin_tables.hpp", "mmx_closest_points_plan.hpp", "mmx_mesh_tables.hpp", "mmx_closest_points_on_mesh_plan.hpp", "mmx_vertex_constraints.hpp", "mmx_skin_normal_equations_plan.hpp", os.path.join("..", "..", "include", "mmx.h")]
 ARCH = "gfx950"
 
 

@@ -39,6 +39,8 @@ SYMBOLS = [
     "mmx_vertex_normals_backward", "mmx_vertex_normals_host", "mmx_vertex_normals_backward_host", "mmx_host_mesh_tables",
     "mmx_closest_points_on_mesh", "mmx_closest_points_on_mesh_host", "mmx_closest_points_on_mesh_plan",
     "mmx_skin_normal_equations", "mmx_skin_normal_equations_host",
+    "mmx_skin_normal_equations_split", "mmx_skin_normal_equations_split_host", "mmx_skin_normal_equations_workspace_bytes",
+    "mmx_skin_normal_equations_plan", "mmx_skin_normal_equations_auto_parts", "mmx_skin_normal_equations_part_range",
     "mmx_eval_jacobian_host", "mmx_eval_skeleton_state_host", "mmx_host_tables", "mmx_debug_fused_normal_equations", "mmx_debug_tree_normal_equations",
     "mmx_host_elimination_order", "mmx_host_tile_structure", "mmx_host_tile_level_schedule", "mmx_host_f64_assembly_list", "mmx_problem_tile_structure", "mmx_host_live_joints",
     "mmx_comm_unique_id", "mmx_comm_create", "mmx_comm_create_all", "mmx_comm_world_size", "mmx_comm_rank",
@@ -126,6 +128,9 @@ def lib() -> C.CDLL:
         getattr(L, name).argtypes = list(types)
     L.mmx_skin_normal_equations.argtypes = list(_abi.SKIN_NORMAL_EQUATIONS_ARGTYPES)
     L.mmx_skin_normal_equations_host.argtypes = list(_abi.SKIN_NORMAL_EQUATIONS_ARGTYPES[:-1])
+    for name, types in _abi.SKIN_NORMAL_EQUATIONS_SPLIT_ARGTYPES.items():
+        getattr(L, name).argtypes = list(types)
+    L.mmx_skin_normal_equations_workspace_bytes.restype = C.c_int64
     L.mmx_eval_jacobian_host.argtypes = [vp, vp, vp, vp, vp, i32]
     L.mmx_eval_skeleton_state_host.argtypes = [vp, vp, vp]
     L.mmx_debug_tree_normal_equations.argtypes = [vp, vp, vp, vp, vp]
@@ -319,6 +324,30 @@ def closest_points_on_mesh_plan(batch: int, num_source: int, num_triangles: int)
     s, t, w = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     _check(lib().mmx_closest_points_on_mesh_plan(int(batch), int(num_source), int(num_triangles), C.byref(s), C.byref(t), C.byref(w)))
     return dict(sources_per_workgroup=s.value, triangle_tile=t.value, triangle_ways=w.value)
+
+
+def skin_normal_equations_plan(batch: int, count: int, *, plane: bool, compute_units: int, workgroups_per_cu: int = 2) -> int:
+    """The parts a split call with parts = 0 takes (mmx_skin_normal_equations_plan, no GPU needed): `count` plane (one row
+    each) or position (three rows each) constraints per instance on a device of `compute_units` compute units that hold
+    `workgroups_per_cu` of the call's workgroups each."""
+    parts = C.c_int32(0)
+    _check(lib().mmx_skin_normal_equations_plan(
+        int(batch), _abi.MMX_VC_PLANE if plane else _abi.MMX_VC_POSITION, int(count), int(compute_units), int(workgroups_per_cu), C.byref(parts)))  # fmt: skip
+    return parts.value
+
+
+def skin_normal_equations_part_range(tiles: int, parts: int, part: int):
+    """(begin, end, effective_parts): the tiles [begin, end) that part `part` owns when `tiles` 32-row tiles are divided over
+    `parts` parts, and min(parts, tiles) (mmx_skin_normal_equations_part_range, no GPU needed)."""
+    b, e, pe = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(lib().mmx_skin_normal_equations_part_range(int(tiles), int(parts), int(part), C.byref(b), C.byref(e), C.byref(pe)))
+    return b.value, e.value, pe.value
+
+
+def skin_normal_equations_workspace_bytes(batch: int, num_enabled: int, parts: int) -> int:
+    """Bytes of workspace a split call needs (mmx_skin_normal_equations_workspace_bytes, no GPU needed): 0 for parts <= 1,
+    -1 for an argument out of range."""
+    return int(lib().mmx_skin_normal_equations_workspace_bytes(int(batch), int(num_enabled), int(parts)))
 
 
 def closest_points(source, target, max_dist=float("inf"), source_normals=None, target_normals=None, min_normal_dot=0.0, want_dist2=True, want_points=True):
@@ -862,7 +891,7 @@ class Problem:
 
     def vertex_normal_equations(
         self, skin, theta, target, *, vertex=None, barycentric=None, normal=None, weight=None, rest=None, function_weight=1.0,
-        want=("jtj", "jtr", "err"),
+        want=("jtj", "jtr", "err"), parts=1, workspace=None,
     ):
         """Gauss-Newton terms of vertex constraints on `skin` (mmx_skin_normal_equations): (jtj [B,n,n] float32, jtr [B,n]
         float32, err [B] float64) over the enabled parameters in the layout of normal_equations, so that the two add and a
@@ -872,7 +901,14 @@ class Problem:
         barycentric [B,C,3]: what Mesh.closest_points returns as faces[face_index] and barycentric); normal [B,C,3] makes the
         constraints point-to-plane, n . (x - target), the normal used as given; weight [B,C] float or bool (a `valid` mask),
         None = 1; rest [B,V,3] per-instance rest positions; a constraint whose weight is not > 0 or with an index outside
-        [0, V) contributes exact zeros.  float32 / int32 cuda tensors; one kernel on the current stream."""
+        [0, V) contributes exact zeros.  float32 / int32 cuda tensors; one kernel on the current stream.
+
+        parts > 1 divides every instance's 32-row tiles over that many workgroups and adds the partial results in a fixed
+        order with a second kernel (mmx_skin_normal_equations_split: for few instances against a dense mesh); "auto" or 0
+        takes what vertex_normal_equations_parts reports, which depends on the batch size -- pin `parts` for identical bits
+        across batch sizes.  `workspace` is an optional preallocated uint8 cuda tensor of at least
+        skin_normal_equations_workspace_bytes(B, n, parts) bytes (needed for graph capture); without it a torch.empty per
+        call takes its place.  parts = 1 (the default) is the unsplit call."""
         import torch
 
         theta = self._theta(theta)
@@ -905,8 +941,37 @@ class Problem:
             _abi.MMX_VC_PLANE if normal is not None else _abi.MMX_VC_POSITION, Cn, S, float(function_weight),
             *(None if t is None else t.data_ptr() for t in (vertex, barycentric, target, normal, weight, rest)),
         )  # fmt: skip
-        _check(lib().mmx_skin_normal_equations(self._h, skin._h, C.byref(d), _dev(theta), _dev(jtj), _dev(jtr), _dev(err), _stream_ptr()))
+        if parts == 1 and workspace is None:
+            _check(lib().mmx_skin_normal_equations(self._h, skin._h, C.byref(d), _dev(theta), _dev(jtj), _dev(jtr), _dev(err), _stream_ptr()))
+            return jtj, jtr, err
+        parts = 0 if parts == "auto" else int(parts)
+        if workspace is None:
+            resolved = parts
+            if parts == 0:
+                q = C.c_int32(0)
+                _check(lib().mmx_skin_normal_equations_auto_parts(self._h, skin._h, C.byref(d), C.byref(q)))
+                resolved = q.value
+            need = skin_normal_equations_workspace_bytes(B, n, resolved)
+            if need > 0:
+                workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        if workspace is not None:
+            if not isinstance(workspace, torch.Tensor):
+                raise TypeError("workspace must be a torch.Tensor")
+            if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+                raise ValueError("workspace must be a contiguous uint8 cuda tensor")
+        _check(lib().mmx_skin_normal_equations_split(
+            self._h, skin._h, C.byref(d), _dev(theta), _dev(jtj), _dev(jtr), _dev(err), parts,
+            None if workspace is None else workspace.data_ptr(), 0 if workspace is None else int(workspace.numel()), _stream_ptr()))  # fmt: skip
         return jtj, jtr, err
+
+    def vertex_normal_equations_parts(self, skin, count, *, plane, corners=1):
+        """The parts that vertex_normal_equations(..., parts="auto") takes for `count` constraints per instance (plane: one
+        row each, else three) with `corners` vertices each, on this problem's batch and device
+        (mmx_skin_normal_equations_auto_parts)."""
+        d = _abi.VertexConstraints(_abi.MMX_VC_PLANE if plane else _abi.MMX_VC_POSITION, int(count), int(corners), 1.0, None, None, None, None, None, None)
+        q = C.c_int32(0)
+        _check(lib().mmx_skin_normal_equations_auto_parts(self._h, skin._h, C.byref(d), C.byref(q)))
+        return q.value
 
     def jtj_history(self, theta_init, parameter_history, iterations, regularization, out=None):
         """GaussNewtonSolverT's iterationHistory_["jtj"] (gauss_newton_solver.cpp:262-279) for a finished solve: entry i of

@@ -28,6 +28,7 @@
 #include "mmx_skin_tables.hpp"
 #include "mmx_solve_plan.hpp"
 #include "mmx_vertex_constraints.hpp"
+#include "mmx_skin_normal_equations_plan.hpp"
 
 namespace {
 
@@ -2734,6 +2735,64 @@ int32_t mmx_skin_points_backward_host(
 }
 
 // ---- Gauss-Newton terms of vertex constraints on a skin (mmx_skin_normal_equations.hip; intake: mmx_vertex_constraints.cpp)
+} // extern "C"
+
+// the intake both device entries share: the refusals of mmx_skin_normal_equations in their order (pure host), then the
+// kernel's descriptors.  `ldsBytes` (optional) receives the call's LDS size.
+static int32_t skinNormalEquationsIntake(
+    const char* name,
+    mmx_problem* pb,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* c,
+    bool haveTheta,
+    bool haveOutput,
+    mmx::SkinNeColumnsDev* cols,
+    mmx::VertexConstraintsDev* vc,
+    size_t* ldsBytes) {
+  MMX_TRY(checkProblem(pb, false));
+  if (skin == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, std::string(name) + ": skin handle is null");
+  }
+  const mmx::ProblemDev& d = pb->dev;
+  const int32_t nsrc = int32_t(pb->tables.colSources.size());
+  mmx::VertexConstraintsFacts f;
+  f.sameRig = skin->rig == pb->rig;
+  f.haveTheta = haveTheta;
+  f.haveOutput = haveOutput;
+  f.skinVertices = skin->dev.V;
+  f.solved = d.n;
+  if (c != nullptr && (c->corners == 1 || c->corners == 3) && d.n >= 1 && d.n <= mmx::kSkinNeMaxSolved) {
+    f.ldsBytes = mmx::skinNormalEquationsLdsBytes(pb->rig->J, pb->rig->P, d.n, nsrc, c->corners, skin->dev.K);
+  }
+  std::string err;
+  const int32_t rc = mmx::checkVertexConstraints(c, f, err);
+  if (rc != MMX_OK) {
+    return fail(rc, std::string(name) + ": " + err);
+  }
+  cols->n = d.n, cols->nsrc = nsrc;
+  cols->enabledList = d.enabledList, cols->colStart = d.colStart, cols->colSources = d.colSources, cols->jointTin = d.jointTin;
+  vc->type = c->type, vc->C = c->count, vc->S = c->corners, vc->fw = c->function_weight;
+  vc->vertex = c->vertex, vc->bary = c->corners == 3 ? c->barycentric : nullptr, vc->target = c->target;
+  vc->normal = c->type == MMX_VC_PLANE ? c->normal : nullptr, vc->weight = c->weight, vc->rest = c->rest;
+  if (ldsBytes != nullptr) {
+    *ldsBytes = f.ldsBytes;
+  }
+  return MMX_OK;
+}
+
+// parts = 0: the plan, fed with the device's compute units and the workgroups of this call's LDS size a compute unit holds
+static int32_t skinNormalEquationsAutoParts(const char* name, mmx_problem* pb, int32_t type, int32_t count, size_t ldsBytes, int32_t* parts) {
+  int cus = 0;
+  MMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pb->rig->device));
+  const int32_t perCu = 2 * ldsBytes <= size_t(160) * 1024 ? 2 : 1; // (registers bind at two: DESIGN.md)
+  if (!mmx::skinNePlan(pb->B, type, count, cus, perCu, parts)) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, std::string(name) + ": the plan refuses the batch, count, type or compute-unit count");
+  }
+  return MMX_OK;
+}
+
+extern "C" {
+
 int32_t mmx_skin_normal_equations(
     mmx_problem* pb,
     mmx_skin* skin,
@@ -2744,53 +2803,147 @@ int32_t mmx_skin_normal_equations(
     double* err_dev,
     void* stream) {
   MMX_ZONE("mmx_skin_normal_equations (vertex constraints: JtJ, JtR, error)");
-  MMX_TRY(checkProblem(pb, false));
-  if (skin == nullptr) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_normal_equations: skin handle is null");
-  }
-  const mmx::ProblemDev& d = pb->dev;
-  const int32_t nsrc = int32_t(pb->tables.colSources.size());
-  mmx::VertexConstraintsFacts f;
-  f.sameRig = skin->rig == pb->rig;
-  f.haveTheta = theta_dev != nullptr;
-  f.haveOutput = jtj_dev != nullptr || jtr_dev != nullptr || err_dev != nullptr;
-  f.skinVertices = skin->dev.V;
-  f.solved = d.n;
-  if (c != nullptr && (c->corners == 1 || c->corners == 3) && d.n >= 1 && d.n <= mmx::kSkinNeMaxSolved) {
-    f.ldsBytes = mmx::skinNormalEquationsLdsBytes(pb->rig->J, pb->rig->P, d.n, nsrc, c->corners, skin->dev.K);
-  }
-  std::string err;
-  const int32_t rc = mmx::checkVertexConstraints(c, f, err);
-  if (rc != MMX_OK) {
-    return fail(rc, "mmx_skin_normal_equations: " + err);
-  }
   mmx::SkinNeColumnsDev cols{};
-  cols.n = d.n, cols.nsrc = nsrc;
-  cols.enabledList = d.enabledList, cols.colStart = d.colStart, cols.colSources = d.colSources, cols.jointTin = d.jointTin;
   mmx::VertexConstraintsDev vc{};
-  vc.type = c->type, vc.C = c->count, vc.S = c->corners, vc.fw = c->function_weight;
-  vc.vertex = c->vertex, vc.bary = c->corners == 3 ? c->barycentric : nullptr, vc.target = c->target;
-  vc.normal = c->type == MMX_VC_PLANE ? c->normal : nullptr, vc.weight = c->weight, vc.rest = c->rest;
+  MMX_TRY(skinNormalEquationsIntake(
+      "mmx_skin_normal_equations", pb, skin, c, theta_dev != nullptr, jtj_dev != nullptr || jtr_dev != nullptr || err_dev != nullptr, &cols, &vc,
+      nullptr));
   MMX_HIP(hipSetDevice(pb->rig->device));
   MMX_HIP(mmx::launchSkinNormalEquations(pb->rigDev, cols, skin->dev, vc, pb->B, theta_dev, jtj_dev, jtr_dev, err_dev, static_cast<hipStream_t>(stream)));
   return MMX_OK;
 }
 
-int32_t mmx_skin_normal_equations_host(
+int32_t mmx_skin_normal_equations_split(
+    mmx_problem* pb,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* c,
+    const float* theta_dev,
+    float* jtj_dev,
+    float* jtr_dev,
+    double* err_dev,
+    int32_t parts,
+    void* workspace_dev,
+    int64_t workspace_bytes,
+    void* stream) {
+  MMX_ZONE("mmx_skin_normal_equations_split (vertex constraints over several workgroups per instance)");
+  static const char* kName = "mmx_skin_normal_equations_split";
+  mmx::SkinNeColumnsDev cols{};
+  mmx::VertexConstraintsDev vc{};
+  size_t ldsBytes = 0;
+  MMX_TRY(skinNormalEquationsIntake(
+      kName, pb, skin, c, theta_dev != nullptr, jtj_dev != nullptr || jtr_dev != nullptr || err_dev != nullptr, &cols, &vc, &ldsBytes));
+  std::string err;
+  int32_t rc = mmx::checkSkinNeParts(parts, err);
+  if (rc != MMX_OK) {
+    return fail(rc, std::string(kName) + ": " + err);
+  }
+  mmx::SkinNeSplitFacts f;
+  f.batch = pb->B, f.solved = cols.n, f.type = vc.type, f.count = vc.C;
+  f.requested = parts, f.parts = parts;
+  if (parts == 0) {
+    MMX_TRY(skinNormalEquationsAutoParts(kName, pb, vc.type, vc.C, ldsBytes, &f.parts));
+  }
+  f.haveWorkspace = workspace_dev != nullptr;
+  f.workspaceAddress = reinterpret_cast<uintptr_t>(workspace_dev);
+  f.workspaceBytes = workspace_bytes;
+  rc = mmx::checkSkinNeSplit(f, err);
+  if (rc != MMX_OK) {
+    return fail(rc, std::string(kName) + ": " + err);
+  }
+  MMX_HIP(hipSetDevice(pb->rig->device));
+  MMX_HIP(mmx::launchSkinNormalEquationsSplit(
+      pb->rigDev, cols, skin->dev, vc, pb->B, theta_dev, jtj_dev, jtr_dev, err_dev, f.parts, workspace_dev, static_cast<hipStream_t>(stream)));
+  return MMX_OK;
+}
+
+int64_t mmx_skin_normal_equations_workspace_bytes(int32_t batch, int32_t num_enabled, int32_t parts) {
+  return mmx::skinNeWorkspaceBytes(batch, num_enabled, parts);
+}
+
+int32_t mmx_skin_normal_equations_plan(
+    int32_t batch, int32_t type, int32_t count, int32_t compute_units, int32_t workgroups_per_cu, int32_t* parts_out) {
+  int32_t parts = 0;
+  if (!mmx::skinNePlan(batch, type, count, compute_units, workgroups_per_cu, &parts)) {
+    return fail(
+        MMX_ERR_INVALID_ARGUMENT,
+        "mmx_skin_normal_equations_plan: batch, count, compute_units and workgroups_per_cu must be >= 1 and type MMX_VC_POSITION or MMX_VC_PLANE");
+  }
+  if (parts_out != nullptr) {
+    *parts_out = parts;
+  }
+  return MMX_OK;
+}
+
+int32_t mmx_skin_normal_equations_part_range(
+    int32_t tiles, int32_t parts, int32_t part, int32_t* begin_out, int32_t* end_out, int32_t* effective_parts_out) {
+  if (tiles < 1 || parts < 1 || parts > mmx::kSkinNeMaxParts || part < 0 || part >= mmx::skinNeEffectiveParts(parts, tiles)) {
+    return fail(
+        MMX_ERR_INVALID_ARGUMENT,
+        "mmx_skin_normal_equations_part_range: tiles must be >= 1, parts in 1..MMX_SKIN_NE_MAX_PARTS and part in [0, min(parts, tiles))");
+  }
+  const int32_t pe = mmx::skinNeEffectiveParts(parts, tiles);
+  if (begin_out != nullptr) {
+    *begin_out = mmx::skinNePartBegin(part, tiles, pe);
+  }
+  if (end_out != nullptr) {
+    *end_out = mmx::skinNePartBegin(part + 1, tiles, pe);
+  }
+  if (effective_parts_out != nullptr) {
+    *effective_parts_out = pe;
+  }
+  return MMX_OK;
+}
+
+int32_t mmx_skin_normal_equations_auto_parts(mmx_problem* pb, mmx_skin* skin, const mmx_vertex_constraints* c, int32_t* parts_out) {
+  static const char* kName = "mmx_skin_normal_equations_auto_parts";
+  MMX_TRY(checkProblem(pb, false));
+  if (skin == nullptr || c == nullptr) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, std::string(kName) + ": skin / constraints is null");
+  }
+  if (skin->rig != pb->rig) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, std::string(kName) + ": the skin was created on another rig than the problem's");
+  }
+  if ((c->type != MMX_VC_POSITION && c->type != MMX_VC_PLANE) || c->count < 1 || (c->corners != 1 && c->corners != 3)) {
+    return fail(MMX_ERR_INVALID_ARGUMENT, std::string(kName) + ": unknown type, count < 1 or corners outside {1, 3}");
+  }
+  const int32_t n = pb->dev.n;
+  if (n < 1 || n > mmx::kSkinNeMaxSolved) {
+    return fail(MMX_ERR_UNSUPPORTED, std::string(kName) + ": the enabled parameters are outside 1..MMX_SKIN_NE_MAX_SOLVED (128)");
+  }
+  const size_t lds = mmx::skinNormalEquationsLdsBytes(pb->rig->J, pb->rig->P, n, int32_t(pb->tables.colSources.size()), c->corners, skin->dev.K);
+  if (lds > mmx::kVertexConstraintsLdsBudget) {
+    return fail(MMX_ERR_UNSUPPORTED, std::string(kName) + ": the tables do not fit the kernel's LDS budget (160 KB)");
+  }
+  int32_t parts = 0;
+  MMX_TRY(skinNormalEquationsAutoParts(kName, pb, c->type, c->count, lds, &parts));
+  if (parts_out != nullptr) {
+    *parts_out = parts;
+  }
+  return MMX_OK;
+}
+
+} // extern "C"
+
+// the two _host forms: stage the descriptor's arrays and theta, run the device entry (split false: the unsplit one; else the
+// split one with a workspace allocated and freed here -- the device entry refuses a `parts` out of range, after the unsplit
+// refusals as documented), copy the outputs back
+static int32_t skinNormalEquationsHost(
+    const char* name,
     mmx_problem* pb,
     mmx_skin* skin,
     const mmx_vertex_constraints* c,
     const float* theta_host,
     float* jtj_host,
     float* jtr_host,
-    double* err_host) {
-  MMX_ZONE("mmx_skin_normal_equations_host");
+    double* err_host,
+    bool split,
+    int32_t parts) {
   MMX_TRY(checkProblem(pb, false));
   if (skin == nullptr || c == nullptr || theta_host == nullptr) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_normal_equations_host: skin / constraints / theta is null");
+    return fail(MMX_ERR_INVALID_ARGUMENT, std::string(name) + ": skin / constraints / theta is null");
   }
   if (c->count < 1 || (c->corners != 1 && c->corners != 3)) {
-    return fail(MMX_ERR_INVALID_ARGUMENT, "mmx_skin_normal_equations_host: count must be >= 1 and corners 1 or 3");
+    return fail(MMX_ERR_INVALID_ARGUMENT, std::string(name) + ": count must be >= 1 and corners 1 or 3");
   }
   const size_t B = size_t(pb->B), P = size_t(pb->rig->P), n = size_t(pb->dev.n), C = size_t(c->count), S = size_t(c->corners);
   const size_t V = size_t(skin->dev.V);
@@ -2831,9 +2984,30 @@ int32_t mmx_skin_normal_equations_host(
   if (err_host != nullptr) {
     MMX_HIP(skin->sVcErr.ensure(B * sizeof(double)));
   }
-  MMX_TRY(mmx_skin_normal_equations(
-      pb, skin, &dv, skin->sVcTheta.as<float>(), jtj_host ? skin->sVcJtj.as<float>() : nullptr, jtr_host ? skin->sVcJtr.as<float>() : nullptr,
-      err_host ? skin->sVcErr.as<double>() : nullptr, nullptr));
+  float* jtjDev = jtj_host ? skin->sVcJtj.as<float>() : nullptr;
+  float* jtrDev = jtr_host ? skin->sVcJtr.as<float>() : nullptr;
+  double* errDev = err_host ? skin->sVcErr.as<double>() : nullptr;
+  if (!split) {
+    MMX_TRY(mmx_skin_normal_equations(pb, skin, &dv, skin->sVcTheta.as<float>(), jtjDev, jtrDev, errDev, nullptr));
+  } else {
+    int32_t resolved = parts;
+    if (parts == 0) {
+      MMX_TRY(mmx_skin_normal_equations_auto_parts(pb, skin, &dv, &resolved));
+    }
+    const int64_t bytes = mmx::skinNeWorkspaceBytes(pb->B, pb->dev.n, resolved); // (-1 for a problem or parts the call refuses anyway)
+    void* ws = nullptr;
+    if (bytes > 0) {
+      MMX_HIP(hipMalloc(&ws, size_t(bytes)));
+    }
+    const int32_t rc = mmx_skin_normal_equations_split(
+        pb, skin, &dv, skin->sVcTheta.as<float>(), jtjDev, jtrDev, errDev, parts == 0 ? resolved : parts, ws, bytes > 0 ? bytes : 0, nullptr);
+    const hipError_t sync = rc == MMX_OK ? hipDeviceSynchronize() : hipSuccess;
+    if (ws != nullptr) {
+      (void)hipFree(ws);
+    }
+    MMX_TRY(rc);
+    MMX_HIP(sync);
+  }
   MMX_HIP(hipDeviceSynchronize());
   if (jtj_host != nullptr) {
     MMX_HIP(hipMemcpy(jtj_host, skin->sVcJtj.p, B * n * n * sizeof(float), hipMemcpyDeviceToHost));
@@ -2845,6 +3019,33 @@ int32_t mmx_skin_normal_equations_host(
     MMX_HIP(hipMemcpy(err_host, skin->sVcErr.p, B * sizeof(double), hipMemcpyDeviceToHost));
   }
   return MMX_OK;
+}
+
+extern "C" {
+
+int32_t mmx_skin_normal_equations_host(
+    mmx_problem* pb,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* c,
+    const float* theta_host,
+    float* jtj_host,
+    float* jtr_host,
+    double* err_host) {
+  MMX_ZONE("mmx_skin_normal_equations_host");
+  return skinNormalEquationsHost("mmx_skin_normal_equations_host", pb, skin, c, theta_host, jtj_host, jtr_host, err_host, false, 1);
+}
+
+int32_t mmx_skin_normal_equations_split_host(
+    mmx_problem* pb,
+    mmx_skin* skin,
+    const mmx_vertex_constraints* c,
+    const float* theta_host,
+    float* jtj_host,
+    float* jtr_host,
+    double* err_host,
+    int32_t parts) {
+  MMX_ZONE("mmx_skin_normal_equations_split_host");
+  return skinNormalEquationsHost("mmx_skin_normal_equations_split_host", pb, skin, c, theta_host, jtj_host, jtr_host, err_host, true, parts);
 }
 
 } // extern "C"

@@ -276,6 +276,13 @@ size_t skinNormalEquationsLdsBytes(int J, int P, int n, int nsrc, int S, int K);
 hipError_t launchSkinNormalEquations(
     const RigDev& rig, const SkinNeColumnsDev& cols, const SkinDev& sk, const VertexConstraintsDev& vc, int B, const float* theta, float* H,
     float* g, double* err, hipStream_t stream);
+// mmx_skin_normal_equations_split: every instance's tiles divided over min(parts, tiles) workgroups, their raw partial results
+// in `workspace` (layout and size: mmx_skin_normal_equations_plan.hpp, for min(parts, tiles) parts), then
+// skinNormalEquationsReduceKernel adds them over the parts ascending in double -- two kernel nodes, no atomics, no memset.
+// One effective part is launchSkinNormalEquations itself (one node, workspace not read).
+hipError_t launchSkinNormalEquationsSplit(
+    const RigDev& rig, const SkinNeColumnsDev& cols, const SkinDev& sk, const VertexConstraintsDev& vc, int B, const float* theta, float* H,
+    float* g, double* err, int parts, void* workspace, hipStream_t stream);
 int fusedBlocksFor(int n); // number of 16-wide blocks the fused kernel is instantiated for, or -1
 hipError_t launchFusedSolve(
     const RigDev& rig,

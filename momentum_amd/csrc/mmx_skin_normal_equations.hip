@@ -35,6 +35,7 @@
 #include "mmx_device.hpp"
 #include "mmx_fused_helpers.hpp"
 #include "mmx_kernels.hpp"
+#include "mmx_skin_normal_equations_plan.hpp"
 #include "mmx_tree.hpp"
 
 namespace mmx {
@@ -82,6 +83,17 @@ __host__ __device__ inline size_t skinNeLdsFloats(int J, int P, int n, int nsrc,
   return off;
 }
 
+// kSplit = false: the kernel of the header, one workgroup per instance (sp is not read).  kSplit = true: workgroup blockIdx.x is part
+// blockIdx.x % Pe of instance blockIdx.x / Pe; it repeats the set-up, runs the tile loop over its part's tiles
+// (mmx_skin_normal_equations_plan.hpp) and stores its raw partial results to the workspace instead of H / g / err:
+// the accumulators as the waves hold them ([block][reg][lane]: a wave's store of a register is 64 consecutive floats), per
+// column the double h0 + h1, and the double sum of the 32 row threads' errors in row order.  Nothing of another part is read.
+struct SkinNeSplitDev {
+  SkinNeWorkspace ws; // ws.parts = Pe
+  char* base; // the workspace
+};
+
+template <bool kSplit>
 __global__ void __launch_bounds__(kSneThreads) skinNormalEquationsKernel(
     RigDev rig,
     SkinNeColumnsDev cols,
@@ -90,10 +102,12 @@ __global__ void __launch_bounds__(kSneThreads) skinNormalEquationsKernel(
     const float* __restrict__ theta, // [B][P]
     float* __restrict__ H, // [B][n][n] or null
     float* __restrict__ g, // [B][n] or null
-    double* __restrict__ err) { // [B] or null
+    double* __restrict__ err, // [B] or null
+    SkinNeSplitDev sp) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int kT = kSneThreads;
-  const int b = blockIdx.x, tid = threadIdx.x;
+  const int b = kSplit ? int(blockIdx.x) / sp.ws.parts : int(blockIdx.x), tid = threadIdx.x;
+  const int part = kSplit ? int(blockIdx.x) - b * sp.ws.parts : 0;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   selectInstanceRig(rig, b);
   const int J = rig.J, P = rig.P, n = cols.n, nsrc = cols.nsrc;
@@ -187,8 +201,10 @@ __global__ void __launch_bounds__(kSneThreads) skinNormalEquationsKernel(
   const int gCol = tid & (kSkinNeMaxSolved - 1), gHalf = tid >> 7;
   double gAcc = 0.0, errAcc = 0.0;
 
+  const int tileBegin = kSplit ? skinNePartBegin(part, tiles, sp.ws.parts) : 0;
+  const int tileEnd = kSplit ? skinNePartBegin(part + 1, tiles, sp.ws.parts) : tiles;
 #pragma unroll 1
-  for (int tile = 0; tile < tiles; ++tile) {
+  for (int tile = tileBegin; tile < tileEnd; ++tile) {
     const int row0 = tile * kSneTileRows;
     const int rowEnd = min(rows, row0 + kSneTileRows); // one past the tile's last real row
     const int c0 = plane ? row0 : row0 / 3, c1 = plane ? rowEnd - 1 : (rowEnd - 1) / 3;
@@ -352,7 +368,21 @@ __global__ void __launch_bounds__(kSneThreads) skinNormalEquationsKernel(
   }
 
   // ---- store.  D[row][col] of a block: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-  if (H != nullptr) {
+  if (kSplit) {
+    if (H != nullptr) {
+      float* accWs = reinterpret_cast<float*>(sp.base + sp.ws.accOffset);
+#pragma unroll
+      for (int q = 0; q < kSneMaxBlocksPerWave; ++q) {
+        if (wave + 4 * q < numBlocks) {
+          float* o = accWs + sp.ws.accIndex(b, part, wave + 4 * q) + lane;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            o[64 * r] = acc[q][r];
+          }
+        }
+      }
+    }
+  } else if (H != nullptr) {
     float* Hb = H + size_t(b) * size_t(n) * size_t(n);
 #pragma unroll
     for (int q = 0; q < kSneMaxBlocksPerWave; ++q) {
@@ -378,6 +408,19 @@ __global__ void __launch_bounds__(kSneThreads) skinNormalEquationsKernel(
     ePart[tid] = errAcc;
   }
   __syncthreads();
+  if (kSplit) {
+    if (g != nullptr && tid < n) {
+      reinterpret_cast<double*>(sp.base + sp.ws.gOffset)[sp.ws.gIndex(b, part) + tid] = gPart[tid] + gPart[kSkinNeMaxSolved + tid];
+    }
+    if (err != nullptr && tid == 0) {
+      double e = 0.0;
+      for (int r = 0; r < kSneTileRows; ++r) {
+        e += ePart[r];
+      }
+      reinterpret_cast<double*>(sp.base + sp.ws.errOffset)[sp.ws.errIndex(b, part)] = e;
+    }
+    return;
+  }
   if (g != nullptr && tid < n) {
     g[size_t(b) * n + tid] = float(gPart[tid] + gPart[kSkinNeMaxSolved + tid]);
   }
@@ -387,6 +430,61 @@ __global__ void __launch_bounds__(kSneThreads) skinNormalEquationsKernel(
       e += ePart[r];
     }
     err[b] = e;
+  }
+}
+
+// The second pass of the split: one thread per entry of the lower block triangle (as the waves held it: [block][reg][lane]),
+// per g column and per instance error.  Each sums its entry over the parts ascending, in double, rounds once and stores the
+// entry (and, off the diagonal blocks, its mirror: H is bitwise symmetric as in the unsplit kernel, whose diagonal blocks are
+// symmetric by the order of their products).  Consecutive threads read consecutive addresses of every part.
+__global__ void __launch_bounds__(kSneThreads) skinNormalEquationsReduceKernel(
+    SkinNeWorkspace ws, const char* __restrict__ base, int n, float* __restrict__ H, float* __restrict__ g, double* __restrict__ err) {
+  const int accEntries = ws.numBlocks * kSkinNeBlockFloats;
+  const int groups = (accEntries + ws.nPad + 1 + kSneThreads - 1) / kSneThreads; // workgroups of an instance
+  const int b = int(blockIdx.x) / groups;
+  const int e = (int(blockIdx.x) - b * groups) * kSneThreads + threadIdx.x;
+  if (e < accEntries) {
+    if (H == nullptr) {
+      return;
+    }
+    const int block = e >> 10, r = (e >> 6) & 15, lane = e & 63;
+    const float* src = reinterpret_cast<const float*>(base + ws.accOffset) + ws.accIndex(b, 0, block) + (e & (kSkinNeBlockFloats - 1));
+    const int64_t stride = int64_t(ws.numBlocks) * kSkinNeBlockFloats;
+    double sum = 0.0;
+    for (int p = 0; p < ws.parts; ++p) {
+      sum += double(src[p * stride]);
+    }
+    int I = 0;
+    while ((I + 1) * (I + 2) / 2 <= block) {
+      ++I;
+    }
+    const int Jb = block - I * (I + 1) / 2;
+    const int cj = 32 * Jb + (lane & 31), ri = 32 * I + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (ri < n && cj < n) {
+      float* Hb = H + size_t(b) * size_t(n) * size_t(n);
+      const float v = float(sum);
+      Hb[size_t(ri) * n + cj] = v;
+      if (I != Jb) {
+        Hb[size_t(cj) * n + ri] = v;
+      }
+    }
+  } else if (e < accEntries + ws.nPad) {
+    const int col = e - accEntries;
+    if (g != nullptr && col < n) {
+      const double* src = reinterpret_cast<const double*>(base + ws.gOffset) + ws.gIndex(b, 0) + col;
+      double sum = 0.0;
+      for (int p = 0; p < ws.parts; ++p) {
+        sum += src[size_t(p) * ws.nPad];
+      }
+      g[size_t(b) * n + col] = float(sum);
+    }
+  } else if (e == accEntries + ws.nPad && err != nullptr) {
+    const double* src = reinterpret_cast<const double*>(base + ws.errOffset) + ws.errIndex(b, 0);
+    double sum = 0.0;
+    for (int p = 0; p < ws.parts; ++p) {
+      sum += src[p];
+    }
+    err[b] = sum;
   }
 }
 
@@ -402,11 +500,49 @@ hipError_t launchSkinNormalEquations(
     return hipErrorInvalidValue;
   }
   static LdsLimitCache ldsLimit;
-  hipError_t rc = ldsLimit.ensure(reinterpret_cast<const void*>(skinNormalEquationsKernel), lds);
+  hipError_t rc = ldsLimit.ensure(reinterpret_cast<const void*>(skinNormalEquationsKernel<false>), lds);
   if (rc != hipSuccess) {
     return rc;
   }
-  hipLaunchKernelGGL(skinNormalEquationsKernel, dim3(B), dim3(kSneThreads), lds, stream, rig, cols, sk, vc, theta, H, g, err);
+  hipLaunchKernelGGL(skinNormalEquationsKernel<false>, dim3(B), dim3(kSneThreads), lds, stream, rig, cols, sk, vc, theta, H, g, err, SkinNeSplitDev{});
+  return hipGetLastError();
+}
+
+hipError_t launchSkinNormalEquationsSplit(
+    const RigDev& rig, const SkinNeColumnsDev& cols, const SkinDev& sk, const VertexConstraintsDev& vc, int B, const float* theta, float* H,
+    float* g, double* err, int parts, void* workspace, hipStream_t stream) {
+  const int tiles = skinNeTiles(vc.type, vc.C);
+  if (tiles < 1 || parts < 1) {
+    return hipErrorInvalidValue;
+  }
+  const int pe = skinNeEffectiveParts(parts, tiles);
+  if (pe <= 1) { // one part is the unsplit launch: its bits, one kernel node, no workspace
+    return launchSkinNormalEquations(rig, cols, sk, vc, B, theta, H, g, err, stream);
+  }
+  const size_t lds = skinNormalEquationsLdsBytes(rig.J, rig.P, cols.n, cols.nsrc, vc.S, sk.K);
+  SkinNeSplitDev sp{};
+  if (lds > 160 * 1024 - 64 || workspace == nullptr || !skinNeWorkspaceLayout(B, cols.n, pe, &sp.ws) || int64_t(B) * pe > 0x7fffffffll) {
+    return hipErrorInvalidValue;
+  }
+  sp.base = static_cast<char*>(workspace);
+  static LdsLimitCache ldsLimit;
+  hipError_t rc = ldsLimit.ensure(reinterpret_cast<const void*>(skinNormalEquationsKernel<true>), lds);
+  if (rc != hipSuccess) {
+    return rc;
+  }
+  hipLaunchKernelGGL(skinNormalEquationsKernel<true>, dim3(B * pe), dim3(kSneThreads), lds, stream, rig, cols, sk, vc, theta, H, g, err, sp);
+  rc = hipGetLastError();
+  if (rc != hipSuccess) {
+    return rc;
+  }
+  const int entries = sp.ws.numBlocks * kSkinNeBlockFloats + sp.ws.nPad + 1;
+  const int64_t groups = int64_t(B) * ((entries + kSneThreads - 1) / kSneThreads);
+  if (groups > 0x7fffffffll) {
+    return hipErrorInvalidValue;
+  }
+  hipLaunchKernelGGL(
+      skinNormalEquationsReduceKernel, dim3(unsigned(groups)), dim3(kSneThreads), 0, stream, sp.ws, static_cast<const char*>(workspace),
+      cols.n, H, g, err);
   return hipGetLastError();
 }
 

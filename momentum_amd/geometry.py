@@ -137,7 +137,7 @@ def find_closest_points_on_mesh(points_source, vertices_target, faces_target, *,
 
 def vertex_normal_equations(
     problem, skin, theta, target, *, vertex=None, barycentric=None, normal=None, weight=None, rest=None, function_weight=1.0,
-    want=("jtj", "jtr", "err"),
+    want=("jtj", "jtr", "err"), parts=1, workspace=None,
 ):
     """Gauss-Newton terms of vertex constraints on a skinned mesh: capi.Problem.vertex_normal_equations with the outputs of
     the closest-point queries taken as they come.
@@ -150,6 +150,10 @@ def vertex_normal_equations(
 
     Returns (jtj [B, n, n], jtr [B, n], err [B] float64) over the enabled parameters, in the layout of
     problem.normal_equations: the two sets of terms add.  The results carry no autograd graph.
+
+    parts and workspace go to capi.Problem.vertex_normal_equations as they are: parts > 1 (or "auto") divides every instance
+    over several workgroups -- for one scan or a short clip against a dense mesh; an instance's bits depend on its inputs and
+    the effective parts only, and "auto" depends on the batch size.
     """
     import torch
 
@@ -160,5 +164,5 @@ def vertex_normal_equations(
         weight = weight.to(torch.float32)
     return problem.vertex_normal_equations(
         skin, theta.detach().contiguous(), prep(target), vertex=prep(vertex), barycentric=prep(barycentric), normal=prep(normal),
-        weight=prep(weight), rest=prep(rest), function_weight=function_weight, want=want,
+        weight=prep(weight), rest=prep(rest), function_weight=function_weight, want=want, parts=parts, workspace=workspace,
     )  # fmt: skip
