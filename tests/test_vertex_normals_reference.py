@@ -92,3 +92,122 @@ def test_rings():
     one, two = ref.rings(tri, pos.shape[1], 15)
     assert one.sum() == 7 and one[15]  # valence 6
     assert two.sum() == 19 and (two | one).sum() == 19 and not two[60:].any()
+
+
+# ---- the per-entry rules of tests/test_gpu_vertex_normals_entries.py: the meshes, soundness, teeth, the backward reference
+def _variants(name):
+    """(label, positions, triangles, sums given to the backward or None = the forward's, cotangent): what the GPU file runs."""
+    pos, tri, cot = ref.entry_case(name)
+    out = [("forward_sums", pos, tri, None, cot)]
+    if name in ("ladder", "soup_70"):
+        sums, g = ref.arbitrary_sums(pos.shape, 9)
+        out.append(("arbitrary_sums", pos, tri, sums, g))
+    return out
+
+
+def _restated_worst(pos, tri, sums, cot, **fault):
+    """Worst error / bound per output of the numpy restatement of the kernels (with the planted fault)."""
+    fwd = {k: v for k, v in fault.items() if k in ("acc", "diff", "fused", "drop_last")}
+    bwd = {k: v for k, v in fault.items() if k in ("acc", "diff", "drop_last", "swap_corner1")}
+    normals, m = ref.kernel_forward_np(pos, tri, **fwd)
+    given = m if sums is None else sums
+    got = dict(normals=normals, sums=m, position_grad=ref.kernel_backward_np(pos, tri, given, cot, **bwd))
+    rules = ref.forward_rule(pos, tri)
+    rules["position_grad"] = ref.backward_rule(pos, tri, given, cot)
+    return {key: float(ref.rule_ratios(got[key], rules[key]).max()) for key in ref.KEYS}
+
+
+def test_ladder_has_every_list_length_and_an_empty_group():
+    pos, tri = ref.ladder()
+    assert pos.shape == (2, 325, 3)
+    t = ref.capi.host_mesh_tables(325, tri)
+    n = np.diff(t["vertex_start"])
+    assert np.array_equal(n[:64], np.arange(64)) and n[0] == 0  # lane l of group 0: l entries; vertex 0 few (none)
+    assert n[64:128].max() >= 64 and n[64:128].max() % 2 == 0 and n[:64].max() % 2 == 1
+    assert n[192:256].sum() == 0 and n[128:192].max() > 0 and n[256:320].max() == 1  # an empty group between live ones; longest list 1
+    assert n[320:].max() > 1 and (n[320:] == 0).any() and t["max_valence"] == n.max()
+    assert set(t["entry_corner"][t["vertex_start"][63] : t["vertex_start"][64]]) == {0, 1, 2}
+
+
+def test_the_other_entry_meshes_are_what_they_say():
+    for name, V, T in (("soup_70", 70, 200), ("soup_300", 300, 900)):
+        pos, tri = ref.ENTRY_MESHES[name]()
+        n = ref.incidence(tri, V)[1]
+        assert pos.shape[1:] == (V, 3) and tri.shape == (T, 3) and n.min() == 0 and n.max() > (60 if V == 70 else 180) and n[0] == n.max()
+        assert not ref._is_degenerate(tri).any()
+    pos, tri = ref.books()
+    rule = ref.forward_rule(pos, tri)
+    cond = np.linalg.norm(rule["A"], axis=-1) / np.linalg.norm(rule["sums"]["want"], axis=-1)
+    assert tri.shape == (140, 3) and cond.max() > 1e4 and (cond > 1e3).sum() >= 40 and cond.min() < 3.0
+    w64, w32 = ref.vjp_autograd(pos, tri, ref.cotangent(pos.shape, 7), torch.float64), ref.vjp_autograd(pos, tri, ref.cotangent(pos.shape, 7), torch.float32)
+    assert ref.dist(w32["normals"], w64["normals"]).max() > 100 * ref.CAP  # what CAP keeps out of MESHES
+    pos, tri = ref.cm()
+    assert pos.shape == (2, 552, 3) and 100 < np.abs(pos[..., 1]).mean() < 200 and np.abs(pos).max() > 250
+    pos, tri = ref.mixed()
+    start, n, et, ec = ref.incidence(tri, pos.shape[1])
+    dead = ref._is_degenerate(tri)
+    assert dead.sum() == 24 and (n[100:] == 0).all() and (n[70:76] > 0).all() and dead[et[start[70] : start[76]]].all()
+    for v in (0, 3):  # degenerate entries first, in the middle and last in a live vertex's list
+        d = dead[et[start[v] : start[v + 1]]]
+        assert d[0] and d[-1] and d[1:-1].any() and not d.all()
+    m = ref.kernel_forward_np(pos, tri)[1]
+    assert not m[:, 70:].any() and rule["A"].min() >= 0 and ref.forward_rule(pos, tri)["A"][:, 76:100].min() > 0  # exact cancellation, not absence
+    pos, tri = ref.v1()
+    assert pos.shape[1:] == (1, 3) and tri.tolist() == [[0, 0, 0]]
+
+
+@pytest.mark.parametrize("name", list(ref.ENTRY_MESHES))
+def test_the_restated_kernels_hold_every_rule(name):
+    """Soundness: float64 in the kernels' own order, rounded once, is inside every bound -- mostly by the u |x64| of that rounding."""
+    for label, pos, tri, sums, cot in _variants(name):
+        worst = _restated_worst(pos, tri, sums, cot)
+        print(f"{name}/{label}: " + "  ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+        assert max(worst.values()) <= 1.0, (name, label, worst)
+
+
+def test_planted_faults_break_the_rules():
+    """Teeth.  By a factor of at least 10: float32 accumulators (every random mesh, the folds, the arbitrary sums), float32
+    differences on cm.  By exact zeros or errors of order 1: a fused cross product on mixed, the last entry of the longest list
+    dropped on ladder, next and prev exchanged at corner 1."""
+    worst = {}
+    for name in ("ladder", "soup_70", "soup_300", "books", "cm"):
+        for label, pos, tri, sums, cot in _variants(name):
+            w = worst[f"float32_accumulators/{name}/{label}"] = _restated_worst(pos, tri, sums, cot, acc=np.float32)
+            assert w["position_grad"] >= 10.0 and (sums is not None or min(w.values()) >= 10.0), (name, label, w)
+    pos, tri, cot = ref.entry_case("cm")
+    w = worst["float32_differences/cm"] = _restated_worst(pos, tri, None, cot, diff=np.float32)
+    assert min(w.values()) >= 10.0, w
+    pos, tri, cot = ref.entry_case("mixed")
+    w = worst["fused_cross/mixed"] = _restated_worst(pos, tri, None, cot, fused=True)
+    assert w["normals"] == np.inf, w  # a nonzero where a zero is asked
+    fused = ref.kernel_forward_np(pos, tri, fused=True)[1]
+    assert fused[:, 70:].any() and not ref.kernel_forward_np(pos, tri)[1][:, 70:].any()  # (where a product of two differences is not exact)
+    for label, pos, tri, sums, cot in _variants("ladder"):
+        w = worst[f"last_entry_dropped/ladder/{label}"] = _restated_worst(pos, tri, sums, cot, drop_last=True)
+        assert w["position_grad"] >= 1e5 if sums is None else w["position_grad"] <= 1.0, w  # (next to sums of 10^-12 the dropped term is below the float32 rounding of the result)
+        assert w["sums"] >= 1e5 and w["normals"] >= 1e5, w
+    for name in ("ladder", "soup_70", "books"):
+        for label, pos, tri, sums, cot in _variants(name):
+            w = worst[f"next_prev_exchanged_at_corner_1/{name}/{label}"] = _restated_worst(pos, tri, sums, cot, swap_corner1=True)
+            assert w["position_grad"] >= 1e6 and max(w["sums"], w["normals"]) <= 1.0, (name, label, w)
+    for k, w in worst.items():
+        print(f"{k}: " + "  ".join(f"{key} {v:.3g}" for key, v in w.items()))
+
+
+@pytest.mark.parametrize("name", list(ref.ENTRY_MESHES))
+def test_backward_from_given_sums_is_autograd_when_the_sums_are_the_forwards(name):
+    pos, tri, cot = ref.entry_case(name)
+    w = ref.vjp_autograd(pos, tri, cot, torch.float64)
+    got = ref.backward_from_sums64(pos, tri, w["sums"], cot)  # unrounded float64 sums
+    scale = np.abs(w["position_grad"]).max(axis=(1, 2), keepdims=True)
+    assert np.all(np.abs(got - w["position_grad"]) <= 1e-12 * scale), name
+    if name != "mixed":  # (torch's cross product leaves a rounding error where a triangle meets its reversed copy)
+        assert np.abs(ref.forward64(pos, tri)[1] - w["sums"]).max() <= 1e-14 * np.abs(w["sums"]).max()
+
+
+def test_arbitrary_sums_are_what_they_say():
+    sums, cot = ref.arbitrary_sums((2, 325, 3), 9)
+    mag = np.abs(sums.astype(np.float64)).max(-1)
+    assert (mag == 0).sum() == len(range(0, 650, 7)) and mag[mag > 0].min() < 1e-10 and mag.max() > 1e10
+    par = np.linalg.norm(np.cross(sums.astype(np.float64), cot.astype(np.float64)), axis=-1) == 0
+    assert (par & (mag > 0)).sum() >= 650 // 4 and 0.5 <= np.abs(cot[par & (mag > 0)]).max(-1).min() and np.abs(cot[par & (mag > 0)]).max() < 2.0
